@@ -15,9 +15,17 @@ torch.distributed.run (RANK / WORLD_SIZE in the environment; WORLD_SIZE must
 equal --gpus), or, with `--gpus N` and no launcher, this script starts the N
 ranks itself as child processes before anything touches the GPU.
 
-Also reported on rank 0:
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, and `roofline`, which costs no run of its own).  With
+`--dump-outputs DIR` it also writes what the last timed step left with its
+caller (losses, parameters, the rollout's computed planes) as DIR/<name>.npy;
+every seed is fixed, so the same arguments give the same inputs in every run.
+Everything else runs only with `--full`, after the timed steps.
+
+Reported on rank 0:
   roofline      the dominant kernel's achieved FLOP/s from HIP events recorded
                 around each of its launches during the timed region
+With --full also:
   gae_roofline  fused GAE + advantage kernel on a 1M-lane buffer (> Infinity Cache)
   cpu_baseline  the reference's CPU path restated in torch (oracle/torch_ref.py:
                 F.conv2d / linear, autograd, torch.optim.Adam, clip_grad_norm_),
@@ -144,6 +152,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the profiled iteration, the GAE / observation-boundary "
+                        "rooflines, the evaluation latency and the CPU baseline (each has a --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (losses, parameters, the rollout's actions, "
+                        "log-probabilities, values, returns, rewards, masks) as DIR/<name>.npy")
     p.add_argument("--envs", type=int, default=4096, help="env lanes per GPU")
     p.add_argument("--num-steps", type=int, default=128)
     p.add_argument("--ppo-epoch", type=int, default=3)
@@ -540,6 +554,28 @@ def prof_collect(names):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 20   # per array; eight arrays of fp32 stay far below 64 MB
+
+
+def dump_outputs(path, losses, policy, rollouts):
+    """What the last timed step left with its caller, as <path>/<name>.npy: the
+    losses PPO.update returned (fp64), the flat parameter vector it stepped and
+    the rollout planes the step computed (fp32).  An array above DUMP_MAX_ELEMS
+    is a fixed, seeded sample of its elements (the same indices in every run)."""
+    os.makedirs(path, exist_ok=True)
+    params = torch.cat([p.detach().reshape(-1).float() for p in policy.parameters()])
+    arrays = {"params": params, "actions": rollouts.actions, "action_log_probs": rollouts.action_log_probs,
+              "value_preds": rollouts.value_preds, "returns": rollouts.returns, "rewards": rollouts.rewards,
+              "masks": rollouts.masks}
+    np.save(os.path.join(path, "losses.npy"), np.asarray(losses, dtype=np.float64))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -647,16 +683,6 @@ def main():
         iteration()
     torch.cuda.synchronize()
 
-    gae = None
-    if rank == 0 and not args.no_gae_roofline:
-        gae = gae_roofline(device, args.gae_lanes)
-    boundary = None
-    if rank == 0 and not args.no_boundary:
-        boundary = boundary_roofline(device)
-    evalp = None
-    if rank == 0 and not args.no_boundary:
-        evalp = eval_latency(device)
-
     launches_per_iter = 8 * T + 32 * E * M + 64
     names = [k for k in args.profile_kernels.split(",") if k]
     _hip.call("ppo_prof_enable", ",".join(names).encode(), args.steps * launches_per_iter)
@@ -698,10 +724,13 @@ def main():
                      "note": "HIP events around each gradient all-reduce inside the timed region, on the stream "
                              "it runs on (the fc + heads bucket on a side stream during the conv backward)"}
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, policy, rollouts)
+
     # per-kernel breakdown: one more iteration with every kernel family event-timed
     # (outside the timed region: the extra events would perturb `value`)
     pass_info, pass_kernels = None, {}
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         all_names = list(profiled(args.products))
         _hip.call("ppo_prof_enable", ",".join(all_names).encode(), launches_per_iter * 2)
         torch.cuda.synchronize()
@@ -722,6 +751,13 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
+
+    gae = boundary = evalp = None
+    if args.full and not args.no_gae_roofline:
+        gae = gae_roofline(device, args.gae_lanes)
+    if args.full and not args.no_boundary:
+        boundary = boundary_roofline(device)
+        evalp = eval_latency(device)
 
     obs_desc = {"u8": "", "f32": ", fp32 obs storage fed by the f2 chain (--obs f32)",
                 "rgb": ", raw RGB obs storage, decode fused into conv1 (--obs rgb)"}[args.obs]
@@ -766,14 +802,14 @@ def main():
                 "sclk_ghz_pmc": kd.get("sclk_ghz_pmc"), "frac_at_clock": kd.get("frac_at_clock"),
                 "flop_per_launch": round(per_kernel[dom][2] / per_kernel[dom][0])}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         threads = args.cpu_threads or min(16, int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1))
         cpu = cpu_baseline(args.cpu_envs, args.cpu_steps, E, M, H, threads, reps=args.cpu_reps)
     value = N * T * world * args.steps / elapsed
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(1000.0 * elapsed / args.steps, 2), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.half_precision else "f32",
+        "full": args.full, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.half_precision else "f32",
         "split_products": 1 if args.half_precision else args.products,
         "tune": tune or None,
         "data": ("synthetic: counter-hash u8 4x84x84 obs" if args.obs == "u8" else

@@ -1594,6 +1594,40 @@ def test_bench_self_launches_ranks():
     assert r.returncode == 2 and "does not match" in r.stderr
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and runs none
+    of the --full legs; --dump-outputs leaves the last step's losses (those of
+    the result line), parameters and rollout planes as .npy files."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    N, T, H = 64, 8, 64
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--envs", str(N), "--num-steps", str(T), "--hidden", str(H), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - N * T / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    for leg in ("cpu_baseline", "gae_roofline", "boundary_roofline", "eval_latency", "profile_pass"):
+        assert line[leg] is None, leg
+    out = {n[:-4]: np.load(tmp_path / "out" / n) for n in os.listdir(tmp_path / "out")}
+    assert out["losses"].dtype == np.float64
+    np.testing.assert_allclose(out["losses"], line["losses"], rtol=0, atol=1e-6)   # the line rounds to 6 places
+    nparams = sum(int(np.prod(s)) for _, s in O.cnn_param_shapes(H))
+    assert out["params"].shape == (nparams,) and np.isfinite(out["params"]).all()
+    assert out["actions"].shape == (T, N, 1) and out["returns"].shape == (T + 1, N, 1)
+    assert set(np.unique(out["actions"])) <= set(range(8))
+    for name in ("action_log_probs", "value_preds", "returns", "rewards", "masks"):
+        assert out[name].dtype == np.float32 and np.isfinite(out[name]).all(), name
+    assert np.abs(out["returns"][:T]).max() > 0 and np.abs(out["value_preds"][:T]).max() > 0
+
+
 @pytest.mark.parametrize("use_gae", [True, False])
 @pytest.mark.parametrize("ptl", [True, False])
 @pytest.mark.parametrize("T,N", [(128, 8), (128, 1024), (77, 1031), (5, 1), (300, 33), (1, 17)])

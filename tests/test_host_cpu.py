@@ -291,3 +291,55 @@ def test_bench_pmc_lookups_tolerate_other_workloads():
     assert util == {} and clk == {}
     traffic, tsrc = bench.pmc_traffic("conv2_fwd", "no such workload")
     assert traffic is None
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: a plain run asks for none of the extra legs (--full is off by
+    default), and --dump-outputs writes each array as fp32 / fp64 .npy — whole
+    when small, the same seeded sample of DUMP_MAX_ELEMS elements in every call
+    when larger (the sample must not depend on the values)."""
+    import types
+
+    import torch
+
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+    T, N = 3, 5
+    big = bench.DUMP_MAX_ELEMS + 12345
+
+    def fake(seed):
+        g = torch.Generator().manual_seed(seed)
+        pol = types.SimpleNamespace(parameters=lambda: [torch.rand(4, 3, generator=g), torch.rand(7, generator=g)])
+        ro = types.SimpleNamespace(
+            actions=torch.randint(0, 8, (T, N, 1), generator=g), action_log_probs=torch.rand(T, N, 1, generator=g),
+            value_preds=torch.rand(big, generator=g), returns=torch.rand(T + 1, N, 1, generator=g),
+            rewards=torch.rand(T, N, 1, generator=g), masks=torch.ones(T + 1, N, 1))
+        return pol, ro
+
+    pol, ro = fake(0)
+    bench.dump_outputs(str(tmp_path / "a"), (1.5, -2.0, 0.25), pol, ro)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("losses", "params", "actions", "action_log_probs", "value_preds",
+                                                "returns", "rewards", "masks"))
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert got["losses"].dtype == np.float64 and got["losses"].tolist() == [1.5, -2.0, 0.25]
+    assert all(v.dtype == np.float32 for k, v in got.items() if k != "losses")
+    assert got["params"].shape == (19,) and got["actions"].shape == (T, N, 1)
+    assert np.array_equal(got["actions"], ro.actions.numpy().astype(np.float32))
+    assert np.array_equal(got["returns"], ro.returns.numpy())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    # the large plane: DUMP_MAX_ELEMS elements at fixed, increasing positions
+    assert got["value_preds"].shape == (bench.DUMP_MAX_ELEMS,)
+    ramp = types.SimpleNamespace(**dict(vars(ro), value_preds=torch.arange(big, dtype=torch.float32)))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), (0.0, 0.0, 0.0), pol, ramp)
+    idx = np.load(tmp_path / "b" / "value_preds.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "value_preds.npy"))
+    assert np.all(np.diff(idx) > 0) and idx[-1] < big
+    assert np.array_equal(got["value_preds"], ro.value_preds.numpy()[idx.astype(np.int64)])

@@ -14,6 +14,7 @@ if [ "${SUITE:-1}" = 1 ]; then
   rc=$?; tail -2 gpurun_out/${TAG}_smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-1}" = 1 ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the c3 line with every leg (rooflines, CPU baseline)
   timeout -k 10 500 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/${TAG}_bench.log 2>&1
   rc=$?; grep '^{' gpurun_out/${TAG}_bench.log | cut -c1-400; exit $rc
 fi
