@@ -388,6 +388,30 @@ int ppo_heads_train(const float* feat, const float* feat_v, int B, int H, const 
 int ppo_heads_reduce(const float* part_w, const float* part_b, const float* part_loss, int nblk, int H, int A,
                      float* g_wc, float* g_bc, float* g_wa, float* g_ba, double* loss_acc, double inv_b, float scale,
                      int use_clipped_value_loss, void* stream);
+/* The same three for a Box action space: DiagGaussian / FixedNormal
+ * (distributions.py:30-42, 71-86), logstd = the AddBias parameter [A], sigma =
+ * exp(logstd).  Actions are float [rows][A].  act: given != NULL evaluates those
+ * actions; deterministic: action = mean; otherwise action = noise * sigma + mean as
+ * a rounded multiply then a rounded add (torch.normal's arithmetic), noise [N][A]
+ * standard normal draws (host replay) or, when NULL, Box-Muller normals from the
+ * counter RNG (seed, counter, row * A + o).  train: ppo_heads_train with dL/dmean in
+ * the logits' place; part_b holds [blocks][1 + 2A] floats (critic bias, mean
+ * biases, logstd; the -entropy_coef term of dL/dlogstd is added once per launch)
+ * and part_loss slot 3 counts rows whose stored action has a non-finite component.
+ * Launch shape: ppo_heads_train_blocks. */
+int ppo_heads_gauss_act(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                        const float* wa, const float* ba, const float* logstd, int A, const float* noise,
+                        unsigned long long seed, unsigned long long counter, int deterministic, const float* given,
+                        float* value, float* action, float* logp, float* entropy, void* stream);
+int ppo_heads_gauss_train(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
+                          const float* wa, const float* ba, const float* logstd, int A, const int64_t* idx,
+                          long long row0, const float* actions, const float* old_logp, const float* adv,
+                          const float* vpred, const float* ret, float clip, float value_coef, float entropy_coef,
+                          float inv_b, int use_clipped_value_loss, int feat_act, float* dfeat, float* dfeat_v,
+                          float* part_w, float* part_b, float* part_loss, void* stream);
+int ppo_heads_gauss_reduce(const float* part_w, const float* part_b, const float* part_loss, int nblk, int H, int A,
+                           float* g_wc, float* g_bc, float* g_wa, float* g_ba, float* g_logstd, double* loss_acc,
+                           double inv_b, float scale, void* stream);
 /* model.py:77 dist.entropy().mean() */
 int ppo_mean_f32(const float* x, long long n, float* out, void* stream);
 

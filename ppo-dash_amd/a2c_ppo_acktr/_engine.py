@@ -24,6 +24,7 @@ import torch
 
 from . import _dist
 from ._hip import call, ptr, stream
+from .distributions import DiagGaussian
 
 # ppo_trunk_fwd (conv1 -> conv2 -> conv3 in one launch) for u8 rows; PPO_FUSED_TRUNK=0
 # runs the three launches (same-box A/B, tools/ab_bench.sh)
@@ -68,8 +69,14 @@ class CNNEngine:
     """Binds to a Policy whose base is a non-recurrent CNNBase."""
 
     # parameter indices in policy.parameters() order (named_parameters order)
-    W1, B1, W2, B2, W3, B3, W4, B4, WC, BC, WA, BA = range(12)
+    W1, B1, W2, B2, W3, B3, W4, B4, WC, BC, WA, BA, LS = range(13)   # LS: DiagGaussian's logstd (Box only)
     recurrent = False
+
+    def _bind_dist(self, policy):
+        """Categorical (dist.linear) or DiagGaussian (dist.fc_mean, dist.logstd._bias):
+        the distribution's parameters are the last in policy.parameters() order."""
+        self.gauss = isinstance(policy.dist, DiagGaussian)
+        self.A = (policy.dist.fc_mean if self.gauss else policy.dist.linear).weight.shape[0]
 
     def __init__(self, policy, device):
         self.policy = policy
@@ -77,7 +84,7 @@ class CNNEngine:
         base = policy.base
         self.C = base.main[0].weight.shape[1]
         self.H = base.main[7].weight.shape[0]
-        self.A = policy.dist.linear.weight.shape[0]
+        self._bind_dist(policy)
         if self.H > 512 or self.H % 4 != 0:
             raise NotImplementedError(f"hidden_size {self.H}: the HIP engine supports multiples of 4 up to 512")
         if not self.recurrent and base.critic_linear.weight.shape[1] != self.H:
@@ -289,6 +296,10 @@ class CNNEngine:
         value = torch.empty(B, 1, device=self.device)
         if value_only:
             action = logp = ent = None
+        elif self.gauss:
+            action = given if given is not None else torch.empty(B, self.A, device=self.device)
+            logp = torch.empty(B, 1, device=self.device)
+            ent = torch.empty(B, device=self.device) if want_entropy else None
         else:
             action = given if given is not None else torch.empty(B, 1, dtype=torch.int64, device=self.device)
             logp = torch.empty(B, 1, device=self.device)
@@ -298,6 +309,16 @@ class CNNEngine:
             if noise.shape != (B, self.A):
                 raise RuntimeError(f"noise must be [{B},{self.A}]")
         self.rng_counter += 1
+        if self.gauss:
+            if given is not None and given.numel() != B * self.A:
+                raise RuntimeError(f"actions must be [{B},{self.A}], got {tuple(given.shape)}")
+            call("ppo_heads_gauss_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), self.pv(self.LS), self.A, ptr(noise), self.rng_seed,
+                 self.rng_counter, int(bool(deterministic)),
+                 ptr(given.reshape(-1).contiguous() if given is not None else None, torch.float32, "action"),
+                 value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
+                 ptr(logp), ptr(ent), stream())
+            return value, action, logp, ent
         call("ppo_heads_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC), self.pv(self.WA),
              self.pv(self.BA), self.A, ptr(noise), self.rng_seed, self.rng_counter, int(bool(deterministic)),
              ptr(given.reshape(-1).contiguous() if given is not None else None, torch.int64, "action"),
@@ -325,9 +346,22 @@ class CNNEngine:
         ws, dev, H, A, s = self.ws["train"], self.device, self.H, self.A, stream()
         nblk = call("ppo_heads_train_blocks", B)
         part_w = ws.get("part_w", nblk * (1 + A) * H, device=dev)
-        part_b = ws.get("part_b", nblk * (1 + A), device=dev)
+        part_b = ws.get("part_b", nblk * (1 + (2 * A if self.gauss else A)), device=dev)
         part_l = ws.get("part_l", nblk * 4, device=dev)
         inv_b = 1.0 / B
+        if self.gauss:
+            if storage.actions.shape[-1] != A:
+                raise RuntimeError(f"storage holds {storage.actions.shape[-1]} action dimensions, the policy {A}")
+            call("ppo_heads_gauss_train", feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), self.pv(self.LS), A, idx.data_ptr(), 0,
+                 ptr(storage.actions, torch.float32, "storage.actions"), storage.action_log_probs.data_ptr(),
+                 adv.data_ptr(), storage.value_preds.data_ptr(), storage.returns.data_ptr(), hp["clip"],
+                 hp["value_coef"], hp["entropy_coef"], inv_b, int(hp["use_clipped_value_loss"]), int(feat_act),
+                 dfeat.data_ptr(), ptr(dfeat_v), part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), s)
+            call("ppo_heads_gauss_reduce", part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), nblk, H, A,
+                 self.gv(self.WC), self.gv(self.BC), self.gv(self.WA), self.gv(self.BA), self.gv(self.LS),
+                 loss_acc.data_ptr(), inv_b, 1.0, s)
+            return
         call("ppo_heads_train", feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC), self.pv(self.BC), self.pv(self.WA),
              self.pv(self.BA), A, idx.data_ptr(), 0, storage.actions.data_ptr(), storage.action_log_probs.data_ptr(),
              adv.data_ptr(), storage.value_preds.data_ptr(), storage.returns.data_ptr(), hp["clip"], hp["value_coef"],
@@ -450,7 +484,7 @@ class RecurrentEngine(CNNEngine):
     Parameter order: gru.{weight_ih, weight_hh, bias_ih, bias_hh}, main.*, critic, dist."""
 
     GIH, GHH, GBI, GBH = range(4)
-    W1, B1, W2, B2, W3, B3, W4, B4, WC, BC, WA, BA = range(4, 16)
+    W1, B1, W2, B2, W3, B3, W4, B4, WC, BC, WA, BA, LS = range(4, 17)
     recurrent = True
 
     def __init__(self, policy, device):
@@ -533,7 +567,8 @@ class RecurrentEngine(CNNEngine):
             self.status[2].zero_()
             raise RuntimeError("evaluate_actions: the persistent GRU kernel timed out (its outputs are invalid; "
                                "ppo_gru_persist_set(0) selects the per-step launches)")
-        value, _, logp, ent = self._heads(hout, R, given=action.to(self.device, torch.int64), want_entropy=True)
+        value, _, logp, ent = self._heads(hout, R, want_entropy=True,
+                                          given=action.to(self.device, torch.float32 if self.gauss else torch.int64))
         return value, logp, ent, hout[(T - 1) * N:]
 
     @_with_precision
@@ -590,7 +625,7 @@ class MLPEngine(CNNEngine):
     x = cat(obs, vector_obs); value from the critic tower, logits from the actor's.
     Parameter order: actor.0, actor.2, critic.0, critic.2, critic_linear, dist."""
 
-    AW1, AB1, AW2, AB2, CW1, CB1, CW2, CB2, WC, BC, WA, BA = range(12)
+    AW1, AB1, AW2, AB2, CW1, CB1, CW2, CB2, WC, BC, WA, BA, LS = range(13)
 
     def __init__(self, policy, device):   # noqa: D401 — own init, shares the CNNEngine machinery
         base = policy.base
@@ -602,7 +637,7 @@ class MLPEngine(CNNEngine):
         self.V = base.vector_obs_len
         self.obs_dim = self.I - self.V
         self.Ip = (self.I + 3) // 4 * 4
-        self.A = policy.dist.linear.weight.shape[0]
+        self._bind_dist(policy)
         if self.H % 4 != 0 or self.H > 512:
             raise NotImplementedError(f"MLPBase hidden_size {self.H}: multiples of 4 up to 512")
         self.params = list(policy.parameters())

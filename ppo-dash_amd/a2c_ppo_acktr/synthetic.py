@@ -21,6 +21,16 @@ class Discrete(object):
         self.shape = ()
 
 
+class Box(object):
+    """duck-typed gym.spaces.Box (storage.py:22, model.py:33): only the class name
+    and shape are read; low / high are kept for callers that clip actions"""
+
+    def __init__(self, low=-1.0, high=1.0, shape=(1,)):
+        self.low = low
+        self.high = high
+        self.shape = tuple(shape)
+
+
 class SyntheticVecEnv(object):
     def __init__(self, num_envs, obs_shape=(4, 84, 84), num_actions=8, seed=123, p_done=0.01, device=None):
         self.num_envs = num_envs

@@ -1,0 +1,85 @@
+// Pieces shared by the Categorical (heads.hip) and DiagGaussian (heads_gauss.hip)
+// head kernels: the per-lane head-weight registers, the 1 + A wave-reduced dot
+// products, the activation gradient and the loss-partial reduction.
+#pragma once
+#include "common.h"
+
+namespace {
+
+constexpr int HW = 4;  // waves per block
+
+template <int HC, int AMAX>
+struct HeadW {
+  float wc[HC];
+  float wa[AMAX][HC];
+};
+
+template <int HC, int AMAX>
+__device__ __forceinline__ void load_head_w(HeadW<HC, AMAX>& w, const float* __restrict__ wc,
+                                            const float* __restrict__ wa, int A, int H, int lane) {
+#pragma unroll
+  for (int c = 0; c < HC; ++c) w.wc[c] = lane + 64 * c < H ? wc[lane + 64 * c] : 0.f;
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o)
+#pragma unroll
+    for (int c = 0; c < HC; ++c) w.wa[o][c] = (o < A && lane + 64 * c < H) ? wa[o * H + lane + 64 * c] : 0.f;
+}
+
+// value (from fv) and logits (from f) of one row; all lanes end up with the totals
+template <int HC, int AMAX>
+__device__ __forceinline__ void head_dots(const HeadW<HC, AMAX>& w, const float (&f)[HC], const float (&fv)[HC],
+                                          float& value, float (&z)[AMAX], float bc, const float* __restrict__ ba,
+                                          int A) {
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < HC; ++c) v += fv[c] * w.wc[c];
+  value = wave_sum(v) + bc;
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o) {
+    if (o < A) {
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < HC; ++c) s += f[c] * w.wa[o][c];
+      z[o] = wave_sum(s) + ba[o];
+    } else {
+      z[o] = -INFINITY;
+    }
+  }
+}
+
+// d(pre-activation) from d(output) for the activation that produced y
+__device__ __forceinline__ float act_grad(float d, float y, int act) {
+  if (act == 1) return y > 0.f ? d : 0.f;     // ReLU (threshold_backward)
+  if (act == 2) return d * (1.0f - y * y);    // tanh
+  return d;
+}
+
+// loss partials -> acc[0..3] += {0.5·Σvl/B, -Σal/B, Σent/B, # bad actions} (double, fixed order)
+__global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ part_loss, int nblk,
+                                                          double* __restrict__ loss_acc, double inv_b) {
+  __shared__ double r[4][256];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nblk; b += 256)
+    for (int q = 0; q < 4; ++q) acc[q] += (double)part_loss[(size_t)b * 4 + q];
+  for (int q = 0; q < 4; ++q) r[q][threadIdx.x] = acc[q];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o)
+      for (int q = 0; q < 4; ++q) r[q][threadIdx.x] += r[q][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss_acc[0] += 0.5 * r[0][0] * inv_b;
+    loss_acc[1] += -r[1][0] * inv_b;
+    loss_acc[2] += r[2][0] * inv_b;
+    loss_acc[3] += r[3][0];
+  }
+}
+
+// 64-column chunks per lane, rounded up to an instantiated count (1, 2, 4, 8)
+static inline int hc_of(int H) {
+  const int c = (H + 63) / 64;
+  return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8;
+}
+
+}  // namespace

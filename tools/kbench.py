@@ -110,8 +110,22 @@ def main():
              1, dz3.data_ptr(), None, part.data_ptr(), part.data_ptr() + 4 * nb * 9 * H,
              part.data_ptr() + 4 * nb * (9 * H + 9), s)
 
+    # the Box counterpart: float actions [rows][8], logstd [8], partials with 8 more bias slots
+    st_actf = rn(rows, 8, sc=1.0)
+    hls = rn(8, sc=0.3)
+    part_g = torch.empty(hmax * (9 * H + 17 + 4), device=dev)
+
+    def heads_gauss_train():
+        nb = call("ppo_heads_train_blocks", B)
+        call("ppo_heads_gauss_train", h.data_ptr(), None, B, H, hw.data_ptr(), hw.data_ptr() + 4 * H,
+             hw.data_ptr() + 4 * (H + 1), hw.data_ptr() + 4 * (9 * H + 1), hls.data_ptr(), 8, idx.data_ptr(), 0,
+             st_actf.data_ptr(), st_f[0].data_ptr(), st_f[1].data_ptr(), st_f[2].data_ptr(), st_f[3].data_ptr(), 0.1,
+             0.5, 0.01, 1.0 / B, 1, 1, dz3.data_ptr(), None, part_g.data_ptr(), part_g.data_ptr() + 4 * nb * 9 * H,
+             part_g.data_ptr() + 4 * nb * (9 * H + 17), s)
+
     K = {
         "heads_train": (heads_train, 0.0),
+        "heads_gauss_train": (heads_gauss_train, 0.0),
         "conv1_fwd": (lambda: call("ppo_conv1_fwd", obs.data_ptr(), 1, idx.data_ptr(), 0, 4, B, w1.data_ptr(),
                                    b1.data_ptr(), a1.data_ptr(), s), 2.0 * B * 400 * 32 * 256),
         "conv2_fwd": (lambda: call("ppo_conv2_fwd", a1.data_ptr(), B, pk[0], b2.data_ptr(), a2.data_ptr(), s),
