@@ -1102,10 +1102,9 @@ PPO_API int ppo_gru_variant_get(void) { return g_gru_variant; }
 // which at ~10 us per step kernel were the critical path of the recurrent update.
 // Rows of step t are t*n .. t*n + n - 1; mask of row j at step t: masks[idx[t*n + j]]
 // (idx NULL: masks[t*n + j]).
-// per 32-row group: the step counter, the BPTT's start counter, XCC_ID slots of up
-// to 32 unit blocks (gru_seq_bwd16_kernel's L2 agreement) and the BPTT's path
-// report; layout [G step counters][G start counters][32 G XCC slots][G paths]
-// with G = ceil(n/32), path 1 = sc1 hand-off, 2 = L2 hand-off, 0 = not run
+// per 32-row group: the step counter and the BPTT's report; layout
+// [G step counters][G reports: 1 the group ran the persistent BPTT, 0 not run]
+// with G = ceil(n/32)
 PPO_API int ppo_gru_seq_counters(int n) { return n > 0 ? ceil_div(n, 32) * 2 : 1; }
 
 PPO_API int ppo_gru_seq_fwd_ws(const float* h0, const float* masks, const int64_t* idx, const float* whh,

@@ -22,6 +22,8 @@ import torch
 from oracle import ppo_oracle as O
 from oracle import torch_ref as TR
 from helpers.gradcheck import check_grads as _check_grads
+from helpers.relu_decisions import check_relu_decisions as _check_relu_decisions
+from helpers.relu_decisions import engine_relu_masks as _engine_relu_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -67,44 +69,6 @@ def _check_returns(st, nv):
     np.testing.assert_allclose(stats[1], mean, rtol=1e-6, atol=1e-9)
     np.testing.assert_allclose(np.sqrt(stats[2] / (stats[0] - 1)), std, rtol=1e-5)
     return adv
-
-
-def _engine_relu_masks(eng, B, H):
-    """the ReLU decisions of the engine's training forward of the minibatch just run
-    (its workspace activations a1..a3 and fc output h, NHWC -> the reference's NCHW)"""
-    bufs = eng.ws["train"].bufs
-    a1 = bufs["a1"][:B * 12800].view(B, 20, 20, 32).permute(0, 3, 1, 2)
-    a2 = bufs["a2"][:B * 5184].view(B, 9, 9, 64).permute(0, 3, 1, 2)
-    a3 = bufs["a3"][:B * 1568].view(B, 7, 7, 32).permute(0, 3, 1, 2)
-    h = bufs["h"][:B * H].view(B, H)
-    return [t > 0 for t in (a1, a2, a3, h)]
-
-
-def _check_relu_decisions(p, obs_in, ridx, masks, chunk=4096, rel=1e-5):
-    """every ReLU decision of the engine agrees with float64's, except where the
-    float64 pre-activation is within rel x that layer's max |pre-activation| of 0;
-    returns the number of such flips per layer"""
-    w1, b1, w2, b2, w3, b3, w4, b4 = [t.detach() for t in p[:8]]
-    B = masks[0].shape[0]
-    flips, worst, zmax = [0] * 4, [0.0] * 4, [0.0] * 4
-    with torch.no_grad():
-        for s in range(0, B, chunk):
-            e = min(B, s + chunk)
-            rows = slice(s, e) if ridx is None else ridx[s:e].to(obs_in.device)
-            x = TR._decode(obs_in[rows], w1.device, torch.float64)
-            z1 = TR.conv_unfold(x, w1, b1, 4)
-            z2 = TR.conv_unfold(torch.relu(z1), w2, b2, 2)
-            z3 = TR.conv_unfold(torch.relu(z2), w3, b3, 1)
-            z4 = torch.nn.functional.linear(torch.relu(z3).reshape(e - s, -1), w4, b4)
-            for k, z in enumerate((z1, z2, z3, z4)):
-                d = (z > 0) != masks[k][s:e]
-                zmax[k] = max(zmax[k], z.abs().max().item())
-                if d.any():
-                    flips[k] += int(d.sum())
-                    worst[k] = max(worst[k], z[d].abs().max().item())
-    for k in range(4):
-        assert worst[k] <= rel * zmax[k], (k, flips, worst, zmax)
-    return flips
 
 
 def _obs_setup(kind, N, T, gpu, pol, env):

@@ -231,7 +231,9 @@ def test_recurrent_h256_iteration_replays_reference(gpu):
         agent.optimizer._step_flat = orig
     torch.cuda.synchronize()
     # the BPTT's report (ppo_gru_seq_counters layout: [G step counters][G reports]): 1 = the
-    # group ran the persistent kernel; 0 would mean the step launches ran
+    # group ran the persistent kernel; 0 would mean the step launches ran.  The report is
+    # written at kernel entry: with the clear error word it also finished every step
+    assert int(eng.status[0].item()) == 0
     n = N // Mb
     G = -(-n // 32)
     cnt = eng.ws["train"].bufs["gru_cnt"].cpu().numpy()
