@@ -40,7 +40,7 @@ SIGNATURES = {
     "ppo_gather_f16_to_f32": [c_p, c_p, c_p, c_ll, c_ll, c_p],
     "ppo_synth_env_step": [c_p, c_int, c_ll, c_p, c_p, c_p, c_ull, c_ull, c_f, c_p],
     "ppo_cartpole_step": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_ull, c_ull, c_int, c_p],
-    # gemm.hip
+    # dense.hip (the weight packer), conv1.hip / conv1f.hip, conv2.hip, conv3.hip, trunk.hip, dense.hip
     "ppo_packed_weights_size": [c_int],
     "ppo_packed_offsets": [c_int, c_p],
     "ppo_pack_weights": [c_p, c_p, c_p, c_int, c_p, c_p],
@@ -73,10 +73,12 @@ SIGNATURES = {
     # probe.hip (CU-contention diagnostics)
     "ppo_probe_side_kernel": [c_int, c_int, c_ll, c_p, c_p],
     "ppo_probe_now": [c_p, c_p],
+    # conv3.hip, dense.hip
     "ppo_conv3_wgrad": [c_p, c_p, c_int, c_int, c_p, c_p, c_p],
     "ppo_linear_wgrad": [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
     "ppo_wgrad_reduce": [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_f, c_int, c_p],
     "ppo_colsum": [c_p, c_ll, c_int, c_ll, c_p, c_f, c_int, c_p],
+    # tune.hip
     "ppo_tune_set": [ctypes.c_char_p, c_int],
     "ppo_tune_get": [ctypes.c_char_p],
     # heads.hip

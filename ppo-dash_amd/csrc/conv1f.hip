@@ -43,6 +43,7 @@
 // registers during the previous image).
 #include "igemm.h"
 #include "igemm_x9.h"
+#include "conv1_paths.h"
 
 namespace {
 
@@ -882,12 +883,6 @@ __global__ __launch_bounds__(1024) void conv1_wgrad_x6_kernel(const float* __res
 // holds (idx gather as ppo_conv1_fwd) — and on raw u8 RGB frames with the
 // NormalizeWrapper / FrameStackMono(2) decode fused (SRC_RGB); mbits (nullable):
 // the ReLU mask bits of the output as ppo_conv1_fwd_mask writes them
-int conv1_fwd_rgb_affine(const uint8_t* frames, const int64_t* idx, long long row0, int B, const float* mean,
-                         double stdv, const float* w1, const float* b1, float* out, uint32_t* mbits, void* stream);
-
-int conv1_wgrad_rgb_affine(const float* dz1, const uint8_t* frames, const int64_t* idx, long long row0, int B,
-                           const float* mean, double stdv, int Z, float* slab, float* slab_bias, void* stream);
-
 static int conv1_fwd_x6_launch(int src, const void* obs, const int64_t* idx, long long row0, int B, const float* mean,
                                double stdv, const float* w1, const float* b1, float* out, uint32_t* mbits,
                                void* stream) {
@@ -897,12 +892,12 @@ static int conv1_fwd_x6_launch(int src, const void* obs, const int64_t* idx, lon
                                               hipSuccess || n_cu <= 0)
     n_cu = 256;
   const unsigned nb = (unsigned)(B < n_cu ? B : n_cu);
-  const int np = ppo_tune_get("products");
+  const int np = tune_products();
   hipStream_t st = as_stream(stream);
   int slot;
   const bool prof = ppo_prof_begin(src == SRC_F32 ? "conv1_fwd_f32" : "conv1_fwd_rgb", st, &slot);
   const double rs = 1.0 / stdv;
-  const int dbg = ppo_tune_get("stagger") >> 4;   // timing anatomy (kbench --tune stagger=16*dbg)
+  const int dbg = tune_stagger() >> 4;   // timing anatomy (kbench --tune stagger=16*dbg)
   // kernel form: fp32 rows take the full-K 10-wave kernel (3.3 vs 3.9 ms per 65,536-image
   // minibatch); RGB frames the K-split 8-wave one (5.8-5.9 vs 6.5 ms: the full-K form's
   // 96 weight VGPRs plus the decode's means spill there)
@@ -944,7 +939,7 @@ PPO_API int ppo_conv1_fwd_rgb(const uint8_t* frames, const int64_t* idx, long lo
   PPO_REQUIRE(((uintptr_t)frames & 15) == 0 && (mean == nullptr || ((uintptr_t)mean & 15) == 0),
               "ppo_conv1_fwd_rgb: frames and mean must be 16-B aligned");
   // the affine fold (rgbaff.hip) unless tuned off or the raw mode's truncated grey plane
-  if (ppo_tune_get("rgb_aff") != 0 && !(mean == nullptr && stdv == 1.0))
+  if (tune_key(TK_RGB_AFF) != 0 && !(mean == nullptr && stdv == 1.0))
     return conv1_fwd_rgb_affine(frames, idx, row0, B, mean, stdv, w1, b1, out, mbits, stream);
   return conv1_fwd_x6_launch(SRC_RGB, frames, idx, row0, B, mean, stdv, w1, b1, out, mbits, stream);
 }
@@ -954,12 +949,12 @@ static int conv1_wgrad_x6_launch(int src, const float* dz1, const void* obs, con
   if (B <= 0 || Z <= 0) return 0;
   PPO_REQUIRE((B + Z - 1) / Z <= WMAXIMG, "conv1 wgrad: %d images over %d blocks (at most %d per block)", B, Z,
               WMAXIMG);
-  const int np = ppo_tune_get("products");
+  const int np = tune_products();
   hipStream_t st = as_stream(stream);
   int slot;
   const bool prof = ppo_prof_begin(src == SRC_F32 ? "conv1_wgrad_f32" : "conv1_wgrad_rgb", st, &slot);
   const double rs = 1.0 / stdv;
-  const int dbg = ppo_tune_get("stagger") >> 4;
+  const int dbg = tune_stagger() >> 4;
 #define W1(S, N) \
   conv1_wgrad_x6_kernel<S, N><<<Z, 1024, 0, st>>>(dz1, obs, idx, row0, B, mean, stdv, rs, slab, slab_bias, dbg)
 #define W2(S)                      \
@@ -990,7 +985,7 @@ PPO_API int ppo_conv1_wgrad_rgb(const float* dz1, const uint8_t* frames, const i
   PPO_REQUIRE(B >= 0 && frames != nullptr && stdv != 0.0, "ppo_conv1_wgrad_rgb: B=%d std=%g", B, stdv);
   PPO_REQUIRE(((uintptr_t)frames & 15) == 0 && (mean == nullptr || ((uintptr_t)mean & 15) == 0),
               "ppo_conv1_wgrad_rgb: frames and mean must be 16-B aligned");
-  if (ppo_tune_get("rgb_aff") != 0 && !(mean == nullptr && stdv == 1.0))
+  if (tune_key(TK_RGB_AFF) != 0 && !(mean == nullptr && stdv == 1.0))
     return conv1_wgrad_rgb_affine(dz1, frames, idx, row0, B, mean, stdv, Z, slab, slab_bias, stream);
   return conv1_wgrad_x6_launch(SRC_RGB, dz1, frames, idx, row0, B, mean, stdv, Z, slab, slab_bias, stream);
 }

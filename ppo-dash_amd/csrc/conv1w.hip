@@ -31,6 +31,7 @@
 // Output: the split-K slab [Z][32][256] of u8-integer sums (the reduce applies
 // 1/255) and bias partials [Z][32], as every conv1 wgrad variant.
 #include "igemm_x9.h"
+#include "conv1_paths.h"
 
 namespace {
 

@@ -10,7 +10,7 @@
 // every step (the extra ×1 are exact), which is what runs here.
 //
 // Work split:
-//   gi = x · W_ihᵀ + b_ih         one big GEMM over all T·n_env rows (gemm.hip)
+//   gi = x · W_ihᵀ + b_ih         one big GEMM over all T·n_env rows (dense.hip)
 //   per step t: gh = h_in · W_hhᵀ and the gate cell fused in the epilogue
 //     (tile epilogue: a wave's three 32-column tiles are the r, z, n columns of
 //     the same 32 hidden units, so each lane holds all three pre-activations)

@@ -20,6 +20,7 @@
 // tie conventions), dL/dfeature masked by the fc ReLU, and per-block partial
 // sums of the head weight/bias gradients (deterministic reduce afterwards).
 #include "heads_common.h"   // HW, HeadW, load_head_w, head_dots, act_grad, loss_reduce_kernel, hc_of
+#include "tune.h"
 
 namespace {
 
@@ -534,11 +535,10 @@ int dispatch_act(int HC, const float* feat, const float* feat_v, int N, int H, c
   return PPO_EARG;
 }
 
-static int g_heads_lds = 1;   // ppo_tune_set("heads_lds", 0): the register-weight kernel (A/B)
-
 template <int HC, int AMAX>
 int launch_train(const TrainArgs& a, int blocks, hipStream_t st) {
-  if (g_heads_lds && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
+  // ppo_tune_set("heads_lds", 0): the register-weight kernel (A/B)
+  if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
       ((uintptr_t)a.feat & 15) == 0 && ((uintptr_t)a.dfeat & 15) == 0 && ((uintptr_t)a.part_w & 15) == 0) {
     heads_train_lds_kernel<<<blocks, 64 * HW, 0, st>>>(a);
     PPO_LAUNCH_CHECK("heads_train_lds_kernel");
@@ -587,11 +587,6 @@ PPO_API int ppo_heads_act(const float* feat, const float* feat_v, int N, int H, 
                            action, logp, entropy, st);
   return dispatch_act<16>(HC, feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, deterministic, given, value,
                           action, logp, entropy, st);
-}
-
-int heads_lds_knob(int set, int value) {   // gemm.hip's ppo_tune_set / _get ("heads_lds")
-  if (set) g_heads_lds = value;
-  return g_heads_lds;
 }
 
 PPO_API int ppo_heads_train_blocks(int B) {

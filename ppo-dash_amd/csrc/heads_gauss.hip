@@ -20,8 +20,7 @@
 // The entropy does not depend on the row (d mean(entropy)/d s_o = 1), so its
 // term is added once per launch, by block 0.
 #include "heads_common.h"
-
-int heads_lds_knob(int set, int value);   // heads.hip: ppo_tune_set("heads_lds") covers both LDS-weight kernels
+#include "tune.h"
 
 namespace {
 
@@ -536,7 +535,7 @@ int dispatch_act(int HC, const ActArgs& a, hipStream_t st) {
 
 template <int HC, int AMAX>
 int launch_train(const GaussTrainArgs& a, int blocks, hipStream_t st) {
-  if (heads_lds_knob(0, 0) && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
+  if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
       ((uintptr_t)a.feat & 15) == 0 && ((uintptr_t)a.dfeat & 15) == 0 && ((uintptr_t)a.part_w & 15) == 0) {
     gauss_train_lds_kernel<<<blocks, 64 * HW, 0, st>>>(a);
     PPO_LAUNCH_CHECK("gauss_train_lds_kernel");

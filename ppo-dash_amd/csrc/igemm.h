@@ -1,5 +1,13 @@
-// igemm.h — the fp32-MFMA implicit-GEMM core shared by the CNN trunk
-// (gemm.hip) and the GRU (gru.hip).  See gemm.hip's header for the design.
+// igemm.h — the fp32-MFMA (v_mfma_f32_32x32x2_f32) implicit-GEMM core shared by the
+// generic conv1 problems (conv1.hip), the dense layers (dense.hip) and the GRU
+// (gru.hip), and the problem structs both tile cores (this one, igemm_x9.h) load
+// and store through.
+//
+// MFMA fragment map (guide §3): lane l supplies A[l&31][k=l>>5] and
+// B[k=l>>5][l&31].  Tiles sit in LDS either k-contiguous ([rows][BK], swizzled,
+// read as one ds_read_b128 of 4 k values per lane) or row-contiguous ([BK][rows],
+// read as 4 ds_read_b32); the 4 k values of a lane feed 4 successive MFMAs, so the
+// physical k order inside a BK=16 step is a fixed permutation common to A and B.
 #pragma once
 #include <string.h>
 

@@ -22,6 +22,7 @@
 // wave that owns those rows when WN = 1).
 #pragma once
 #include "igemm.h"
+#include "tune.h"
 
 namespace {
 
@@ -78,12 +79,12 @@ __device__ __forceinline__ f32x4 mma(const bf16x8& a, const bf16x8& b, const f32
   if constexpr (NP >= 6) { PART(m, m) PART(l, h) PART(m, h) PART(h, l) PART(h, m) } \
   PART(h, h)
 
-// split-product count of the launches below (ppo_tune_set("products", 1 | 6 | 9))
-static int g_products = 6;
+// launch KERNEL<NP> for the split-product count ppo_tune_set("products", 1 | 6 | 9)
 #define PPO_LAUNCH_NP(KERNEL, GRID, BLOCK, ST, ...)                   \
   do {                                                                \
-    if (g_products == 9) KERNEL<9><<<GRID, BLOCK, 0, ST>>>(__VA_ARGS__); \
-    else if (g_products == 1) KERNEL<1><<<GRID, BLOCK, 0, ST>>>(__VA_ARGS__); \
+    const int np_ = tune_products();                                  \
+    if (np_ == 9) KERNEL<9><<<GRID, BLOCK, 0, ST>>>(__VA_ARGS__);     \
+    else if (np_ == 1) KERNEL<1><<<GRID, BLOCK, 0, ST>>>(__VA_ARGS__); \
     else KERNEL<6><<<GRID, BLOCK, 0, ST>>>(__VA_ARGS__);              \
   } while (0)
 
@@ -697,13 +698,14 @@ int launch_x9(const P& p, long long M, int N, int Z, hipStream_t st, const char*
   dim3 grid((unsigned)gx, (unsigned)((N + P::BN - 1) / P::BN), (unsigned)Z);
   int slot;
   const bool prof = ppo_prof_begin(name, st, &slot);
+  const int np = tune_products();
   if constexpr (P::SPLIT_STAGE) {
-    if (g_products == 9) igemm_x9s_kernel<P, 9><<<grid, P::NT, 0, st>>>(p);
-    else if (g_products == 1) igemm_x9s_kernel<P, 1><<<grid, P::NT, 0, st>>>(p);
+    if (np == 9) igemm_x9s_kernel<P, 9><<<grid, P::NT, 0, st>>>(p);
+    else if (np == 1) igemm_x9s_kernel<P, 1><<<grid, P::NT, 0, st>>>(p);
     else igemm_x9s_kernel<P, 6><<<grid, P::NT, 0, st>>>(p);
   } else {
-    if (g_products == 9) igemm_x9_kernel<P, 9><<<grid, P::NT, 0, st>>>(p);
-    else if (g_products == 1) igemm_x9_kernel<P, 1><<<grid, P::NT, 0, st>>>(p);
+    if (np == 9) igemm_x9_kernel<P, 9><<<grid, P::NT, 0, st>>>(p);
+    else if (np == 1) igemm_x9_kernel<P, 1><<<grid, P::NT, 0, st>>>(p);
     else igemm_x9_kernel<P, 6><<<grid, P::NT, 0, st>>>(p);
   }
   if (prof) ppo_prof_end(slot, st, flops);

@@ -37,6 +37,7 @@
 #include <mutex>
 
 #include "igemm_x9.h"
+#include "conv1_paths.h"
 
 namespace {
 
@@ -554,7 +555,7 @@ int conv1_fwd_rgb_affine(const uint8_t* frames, const int64_t* idx, long long ro
                                               hipSuccess || n_cu <= 0)
     n_cu = 256;
   const unsigned nb = (unsigned)(B < n_cu ? B : n_cu);
-  const int np = ppo_tune_get("products");
+  const int np = tune_products();
   uint16_t* mb16 = reinterpret_cast<uint16_t*>(mbits);
   int slot;
   const bool prof = ppo_prof_begin("conv1_fwd_rgb", st, &slot);

@@ -1,5 +1,6 @@
 // Small-batch forward launchers (small.hip), internal to libppo_hip.so: the
-// forward entry points of gemm.hip route B <= ppo_tune_get("small_b") here.
+// forward entry points of conv1.hip, conv2.hip, conv3.hip and dense.hip route
+// B <= ppo_tune_get("small_b") here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -6,7 +6,8 @@
 // wave (linears) and the whole chip works on one sample.  Plain fp32 FMAs in a
 // fixed order per element: exact fp32 arithmetic like the reference's CPU
 // path (model.py:169-199 convs, Linear), deterministic.  Dispatched by the
-// forward entry points in gemm.hip when B <= ppo_tune_get("small_b").
+// forward entry points in conv1.hip, conv2.hip, conv3.hip and dense.hip when
+// B <= ppo_tune_get("small_b").
 #include "common.h"
 #include "small.h"
 

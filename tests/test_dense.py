@@ -223,7 +223,7 @@ def _pack_mask3(a3):
 def test_conv3_fwd_mask_bits(gpu, B):
     """ppo_conv3_fwd_mask: the same output as ppo_conv3_fwd (bit-identical; B = 3 takes the
     image-resident kernel instead of the small-batch path, which is within fp32 tolerance)
-    and the ReLU bits of exactly that output, lone output (6, 6) included"""
+    and the ReLU bits of exactly that output, lone output C3_LONE_Q = 42 = (6, 0) included"""
     H_ = _hip()
     w4, packed, pk = _packed(gpu, 64, 13)
     g = torch.Generator().manual_seed(B)

@@ -1033,6 +1033,134 @@ def test_trunk_fwd_equals_three_launches(gpu, B, products):
     assert 0.2 < (r3 > 0).float().mean().item() < 0.8
 
 
+def test_products_knob_reaches_every_kernel_family(gpu):
+    """ppo_tune_set("products") is honoured by every kernel family, whichever source
+    file launches it: each family's output at products = 1 differs from its output at
+    6 in at least one element, and a second run at 6 is bit-identical to the first (a
+    launcher reading a copy of the knob of its own would not follow the change).
+    Families, through their C entry points: conv1 forward on u8, fp32 (conv1f.hip) and
+    RGB rows (the affine fold, rgbaff.hip); conv2 / conv3 forward and ppo_trunk_fwd;
+    conv2 / conv3 dgrad; conv1 / conv2 / conv3 wgrad + ppo_wgrad_reduce; ppo_fc_fwd,
+    ppo_linear_dgrad_ex, ppo_linear_wgrad.  B = 20 images (> small_b = 4, two 16-image
+    lone tiles; Z = 7 wgrad blocks of 2-3 images); dense layers M = 20 rows, H = 64 —
+    ppo_linear_wgrad on the GRU's dW_hh shape [3H][H], which takes the split core (a
+    weight gradient of N < 128 columns runs on fp32 MFMA and has no product count).
+    The accuracy of the one-product mode is test_half.py's business."""
+    Hh = _hip()
+    B, H, Z = 20, 64, 7
+    _, packed, pk = _packed(gpu, H, 71)
+    g = torch.Generator().manual_seed(72)
+    rows = B + 7
+    obs = torch.randint(0, 256, (rows, 4, 84, 84), dtype=torch.uint8, generator=g).cuda()
+    obs_f = (torch.rand(rows, 4, 84, 84, generator=g)).cuda()
+    frames = torch.randint(0, 256, (rows, 84, 84, 3), dtype=torch.uint8, generator=g).cuda()
+    mean = (torch.rand(84, 84, 3, generator=g) * 60 + 20).cuda()
+    idx = torch.randperm(rows, generator=g)[:B].contiguous().cuda()
+    w1 = (torch.randn(32, 4, 8, 8, generator=g) * 0.05).cuda()
+    b1, b2, b3, b4 = [(torch.randn(n, generator=g) * 0.1).cuda() for n in (32, 64, 32, H)]
+    a1 = torch.relu(torch.randn(B, 20, 20, 32, generator=g)).cuda()
+    a2 = torch.relu(torch.randn(B, 9, 9, 64, generator=g)).cuda()
+    a3 = torch.relu(torch.randn(B, 1568, generator=g)).cuda()
+    dz1 = torch.randn(B, 20, 20, 32, generator=g).cuda()
+    dz2 = torch.randn(B, 9, 9, 64, generator=g).cuda()
+    dz3 = torch.randn(B, 7, 7, 32, generator=g).cuda()
+    dy = torch.randn(B, 3 * H, generator=g).cuda()
+    wt = (torch.randn(H, 3 * H, generator=g) * 0.1).cuda()
+    hx = torch.randn(B, H, generator=g).cuda()
+    p = lambda t: t.data_ptr()
+
+    def out(*shape):
+        return torch.zeros(*shape, device=gpu)
+
+    def conv1_u8():
+        o = out(B, 400 * 32)
+        Hh.call("ppo_conv1_fwd", p(obs), 1, p(idx), 0, 4, B, p(w1), p(b1), p(o), _s())
+        return o
+
+    def conv1_f32():
+        o = out(B, 400 * 32)
+        Hh.call("ppo_conv1_fwd_f32", p(obs_f), p(idx), 0, B, p(w1), p(b1), p(o), None, _s())
+        return o
+
+    def conv1_rgb_affine():
+        o = out(B, 400 * 32)
+        Hh.call("ppo_conv1_fwd_rgb", p(frames), p(idx), 0, B, p(mean), 36.31282043457031, p(w1), p(b1), p(o), None,
+                _s())
+        return o
+
+    def conv2_fwd():
+        o = out(B, 81 * 64)
+        Hh.call("ppo_conv2_fwd", p(a1), B, pk[0], p(b2), p(o), _s())
+        return o
+
+    def conv3_fwd():
+        o = out(B, 49 * 32)
+        Hh.call("ppo_conv3_fwd", p(a2), B, pk[1], p(b3), p(o), _s())
+        return o
+
+    def trunk_fwd():
+        o1, o2, o3 = out(B, 400 * 32), out(B, 81 * 64), out(B, 49 * 32)
+        Hh.call("ppo_trunk_fwd", p(obs), p(idx), 0, B, p(w1), p(b1), p(o1), None, pk[0], p(b2), p(o2), None, pk[1],
+                p(b3), p(o3), _s())
+        return torch.cat([o1, o2, o3], 1)
+
+    def conv2_dgrad():
+        o = out(B, 400 * 32)
+        Hh.call("ppo_conv2_dgrad", p(dz2), B, pk[5], p(a1), p(o), _s())
+        return o
+
+    def conv3_dgrad():
+        o = out(B, 81 * 64)
+        Hh.call("ppo_conv3_dgrad", p(dz3), B, pk[4], p(a2), p(o), _s())
+        return o
+
+    def wgrad(name, args, M, NW, kind, a, b, scale):
+        slab, slab_b, gw, gb = out(Z * M * NW), out(Z * M), out(M * NW), out(M)
+        Hh.call(name, *args, B, Z, p(slab), p(slab_b), _s())
+        Hh.call("ppo_wgrad_reduce", p(slab), p(slab_b), Z, M, NW, kind, a, b, p(gw), p(gb), scale, 0, _s())
+        return torch.cat([gw, gb])
+
+    def fc_fwd():
+        o = out(B, H)
+        Hh.call("ppo_fc_fwd", p(a3), B, pk[2], p(b4), H, p(o), H, _s())
+        return o
+
+    def linear_dgrad_ex():
+        o = out(B, H)
+        Hh.call("ppo_linear_dgrad_ex", p(dy), B, 3 * H, p(wt), H, None, 0, 1, p(o), _s())
+        return o
+
+    def linear_wgrad():
+        slab, slab_b = out(3 * H * H), out(3 * H)
+        Hh.call("ppo_linear_wgrad", p(dy), p(hx), B, 3 * H, H, 1, p(slab), p(slab_b), _s())
+        return torch.cat([slab, slab_b])
+
+    families = {
+        "conv1_fwd_u8": conv1_u8, "conv1_fwd_f32": conv1_f32, "conv1_fwd_rgb_affine": conv1_rgb_affine,
+        "conv2_fwd": conv2_fwd, "conv3_fwd": conv3_fwd, "trunk_fwd": trunk_fwd,
+        "conv2_dgrad": conv2_dgrad, "conv3_dgrad": conv3_dgrad,
+        "conv1_wgrad": lambda: wgrad("ppo_conv1_wgrad", (p(dz1), p(obs), 1, p(idx), 0, 4), 32, 256, 0, 0, 0, 1.0 / 255),
+        "conv2_wgrad": lambda: wgrad("ppo_conv2_wgrad", (p(dz2), p(a1)), 64, 512, 1, 4, 32, 1.0),
+        "conv3_wgrad": lambda: wgrad("ppo_conv3_wgrad", (p(dz3), p(a2)), 32, 576, 1, 3, 64, 1.0),
+        "fc_fwd": fc_fwd, "linear_dgrad_ex": linear_dgrad_ex, "linear_wgrad": linear_wgrad,
+    }
+    assert Hh.call("ppo_tune_get", b"rgb_aff") == 1 and Hh.call("ppo_tune_get", b"small_b") < B
+    old = Hh.call("ppo_tune_get", b"products")
+    runs = []
+    try:
+        for products in (6, 1, 6):
+            Hh.call("ppo_tune_set", b"products", products)
+            runs.append({name: fn() for name, fn in families.items()})
+        torch.cuda.synchronize()
+    finally:
+        Hh.call("ppo_tune_set", b"products", old)
+    for name in families:
+        first, one, again = (r[name] for r in runs)
+        assert torch.isfinite(first).all() and first.abs().max() > 0, name
+        assert not torch.equal(one, first), f"{name}: products = 1 changed nothing"
+        assert torch.equal(again, first), f"{name}: products = 6 not restored"
+
+
 @pytest.mark.parametrize("products", [6, 9])
 def test_conv2_fwd_vs_torch(gpu, products):
     """conv2 forward (4x4 stride 2, 20x20x32 -> 9x9x64, bias + ReLU): the

@@ -252,13 +252,17 @@ def test_gemm_plane_swizzle_conflict_free():
 
 
 def test_conv_row_tiles_cover_every_output_once():
-    """Row-tile maps of the standalone conv forwards (gemm.hip conv2_fwd_x9c_body
-    with MT = 5 + conv2_fwd_lone_kernel; conv3_fwd_c3_kernel + conv3_fwd_lone_kernel),
-    restated: every output pixel is computed exactly once, dummy rows write nothing,
-    and a 16-row tile's phase-grid rows collide in residue mod 16 (a bank conflict of
-    the fragment read) at most 2-way.  conv2: v = 10 oy + ox over the 9 x 10 phase
-    grid, m = 9 oy + ox; the lone pixel is v = 80 (m = 72).  conv3: compact rows
-    m = 7 oy + ox < 48 on three tiles, m = 48 lone."""
+    """Row-tile maps of the standalone conv forwards: every output pixel is computed
+    exactly once.  conv2 (conv2_fwd_x9c_body's five row tiles + conv2_fwd_lone_kernel),
+    restated: v = 10 oy + ox over the 9 x 10 phase grid, m = 9 oy + ox, the lone pixel
+    is v = 80 (m = 72); dummy rows write nothing, and a 16-row tile's phase-grid rows
+    collide in residue mod 16 (a bank conflict of the fragment read) at most 2-way.
+    conv3 (conv3_fwd_c3_body + conv3_lone_tiles), read from the source under csrc/: the
+    48 entries of c3_row_q and the lone output (C3_LONE_Y, C3_LONE_X) are the outputs
+    q = 7 oy + ox = 0 .. 48 once each, and every row's tap pixels stay on the 9 x 9
+    input grid."""
+    import glob
+    import re
     vtab = [[None] * 16 for _ in range(5)]
     for tid in range(16):
         t = 0
@@ -275,12 +279,21 @@ def test_conv_row_tiles_cover_every_output_once():
     for row in vtab:
         res = [v % 16 for v in row]
         assert max(res.count(r) for r in set(res)) <= 2
-    conv3 = [16 * t + i for t in range(3) for i in range(16)] + [48]
-    assert sorted(conv3) == list(range(49))
-    # tap pixels of the compact rows stay on the 9 x 9 grid (no pad row reached)
-    for m in range(48):
-        oy, ox = divmod(m, 7)
-        assert 9 * oy + ox + 9 * 2 + 2 <= 80
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    srcs = [open(f).read() for f in sorted(glob.glob(os.path.join(root, "ppo-dash_amd", "csrc", "*")))]
+    tables = [m for s in srcs for m in re.finditer(r"c3_row_q\[48\]\s*=\s*\{([^}]*)\}", s)]
+    lones = [m for s in srcs for m in re.finditer(r"C3_LONE_Y\s*=\s*(\d+)\s*,\s*C3_LONE_X\s*=\s*(\d+)", s)]
+    assert len(tables) == 1 and len(lones) == 1   # one definition of each
+    row_q = [int(x) for x in tables[0].group(1).split(",")]
+    lone_y, lone_x = (int(x) for x in lones[0].groups())
+    assert len(row_q) == 48 and 0 <= lone_y < 7 and 0 <= lone_x < 7
+    assert sorted(row_q + [7 * lone_y + lone_x]) == list(range(49))
+    # tap pixels p0 + 9 ky + kx of every row, the lone one included, stay on the 9 x 9 grid
+    for q in row_q + [7 * lone_y + lone_x]:
+        oy, ox = divmod(q, 7)
+        for ky in range(3):
+            for kx in range(3):
+                assert 0 <= oy + ky < 9 and 0 <= ox + kx < 9 and 0 <= 9 * oy + ox + 9 * ky + kx <= 80
 
 
 def test_bench_pmc_lookups_tolerate_other_workloads():

@@ -3,7 +3,7 @@
 
   python tools/isa_loop.py FILE.s 'igemm_x9_kernel.*DenseReluFwd.*XP128' [--all]
 
-FILE.s comes from `hipcc --offload-arch=gfx950 --cuda-device-only -O3 -S csrc/gemm.hip`.
+FILE.s comes from `hipcc --offload-arch=gfx950 --cuda-device-only -O3 -S csrc/conv2.hip`.
 For each function whose (mangled) name matches the regex, the loops (a label that a
 later s_cbranch / s_branch jumps back to) are listed with their instruction counts by
 class; without --all only the loop holding the most MFMAs is shown.

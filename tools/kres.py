@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of the gfx950 kernels of one source file, from the
 code-object metadata of a device-only assembly build:
-  python tools/kres.py csrc/gemm.hip [name_substring ...]   (run in ppo-dash_amd/)"""
+  python tools/kres.py csrc/conv2.hip [name_substring ...]   (run in ppo-dash_amd/)"""
 import re
 import subprocess
 import sys

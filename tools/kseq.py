@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction-class skeleton of one kernel's gfx950 code, for checking where a
 schedule puts its global loads / stores, waits and barriers:
-  python tools/kseq.py csrc/gemm.hip mangled_name_substring [--waits]   (in ppo-dash_amd/)
+  python tools/kseq.py csrc/conv2.hip mangled_name_substring [--waits]   (in ppo-dash_amd/)
 M mfma, L global/buffer load, S global/buffer store, D LDS-DMA load, r/W ds read/write,
 w s_waitcnt with a vmcnt, | s_barrier; one line per basic block.  --waits lists the
 vmcnt waits with their line in the kernel body; --mem prints every global / buffer
