@@ -22,8 +22,9 @@
  *     process-global configuration: set them from one thread, between launches;
  *   - return 0 on success, a hipError_t or a PPO_E* code otherwise;
  *     ppo_last_error() returns the message of the calling thread's last error;
- *   - storage planes are [T(+1)][N] fp32 (time-major, env-minor), actions i64,
- *     observations u8 (or f32) [rows][C][84][84]; activations NHWC fp32.
+ *   - storage planes are [T(+1)][N] fp32 (time-major, env-minor), actions i64
+ *     (Discrete; Box and MultiBinary store fp32 [rows][A], see ppo_heads_gauss_* and
+ *     ppo_heads_bern_*), observations u8 (or f32) [rows][C][84][84]; activations NHWC fp32.
  */
 #ifndef PPO_HIP_H
 #define PPO_HIP_H
@@ -412,6 +413,29 @@ int ppo_heads_gauss_train(const float* feat, const float* feat_v, int B, int H, 
 int ppo_heads_gauss_reduce(const float* part_w, const float* part_b, const float* part_loss, int nblk, int H, int A,
                            float* g_wc, float* g_bc, float* g_wa, float* g_ba, float* g_logstd, double* loss_acc,
                            double inv_b, float scale, void* stream);
+/* act and train for a MultiBinary action space: Bernoulli / FixedBernoulli
+ * (distributions.py:45-56, 93-104), logits z = f . wa + ba, p = sigmoid(z) in fp32.
+ * Actions are float [rows][A] holding 0.0 or 1.0.  act: given != NULL evaluates those
+ * actions; deterministic: action = (p > 0.5), torch.gt(probs, 0.5); otherwise action =
+ * (noise < p), which is torch.bernoulli(probs) with noise [N][A] the uniform_() draw in
+ * [0, 1) (host replay) or, when NULL, 24-bit uniforms from the counter RNG (seed,
+ * counter, row * A + o).  log_prob = sum_o a z - softplus(z), entropy = sum_o
+ * softplus(-z) + (1 - p) z, both finite for any finite z.  train: ppo_heads_train with
+ * dL/dz_o = g_logp (a_o - p_o) + (entropy_coef / B) z_o p_o (1 - p_o); the parameters
+ * are dist.linear, part_w / part_b / part_loss have ppo_heads_train's layouts and
+ * ppo_heads_reduce sums them.  part_loss slot 3 counts rows whose stored action has a
+ * component that is not exactly 0 or 1 (NaN included).  Launch shape:
+ * ppo_heads_train_blocks. */
+int ppo_heads_bern_act(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                       const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+                       unsigned long long counter, int deterministic, const float* given, float* value,
+                       float* action, float* logp, float* entropy, void* stream);
+int ppo_heads_bern_train(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
+                         const float* wa, const float* ba, int A, const int64_t* idx, long long row0,
+                         const float* actions, const float* old_logp, const float* adv, const float* vpred,
+                         const float* ret, float clip, float value_coef, float entropy_coef, float inv_b,
+                         int use_clipped_value_loss, int feat_act, float* dfeat, float* dfeat_v, float* part_w,
+                         float* part_b, float* part_loss, void* stream);
 /* model.py:77 dist.entropy().mean() */
 int ppo_mean_f32(const float* x, long long n, float* out, void* stream);
 

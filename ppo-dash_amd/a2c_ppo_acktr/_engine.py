@@ -24,7 +24,7 @@ import torch
 
 from . import _dist
 from ._hip import call, ptr, stream
-from .distributions import DiagGaussian
+from .distributions import Bernoulli, DiagGaussian
 
 # ppo_trunk_fwd (conv1 -> conv2 -> conv3 in one launch) for u8 rows; PPO_FUSED_TRUNK=0
 # runs the three launches (same-box A/B, tools/ab_bench.sh)
@@ -73,9 +73,13 @@ class CNNEngine:
     recurrent = False
 
     def _bind_dist(self, policy):
-        """Categorical (dist.linear) or DiagGaussian (dist.fc_mean, dist.logstd._bias):
-        the distribution's parameters are the last in policy.parameters() order."""
-        self.gauss = isinstance(policy.dist, DiagGaussian)
+        """Categorical or Bernoulli (dist.linear) or DiagGaussian (dist.fc_mean,
+        dist.logstd._bias): the distribution's parameters are the last in
+        policy.parameters() order."""
+        self.dist_kind = ("gauss" if isinstance(policy.dist, DiagGaussian) else
+                          "bern" if isinstance(policy.dist, Bernoulli) else "cat")
+        self.gauss = self.dist_kind == "gauss"
+        self.float_actions = self.dist_kind != "cat"   # float [B, A] actions (Box, MultiBinary)
         self.A = (policy.dist.fc_mean if self.gauss else policy.dist.linear).weight.shape[0]
 
     def __init__(self, policy, device):
@@ -296,7 +300,7 @@ class CNNEngine:
         value = torch.empty(B, 1, device=self.device)
         if value_only:
             action = logp = ent = None
-        elif self.gauss:
+        elif self.float_actions:
             action = given if given is not None else torch.empty(B, self.A, device=self.device)
             logp = torch.empty(B, 1, device=self.device)
             ent = torch.empty(B, device=self.device) if want_entropy else None
@@ -309,9 +313,17 @@ class CNNEngine:
             if noise.shape != (B, self.A):
                 raise RuntimeError(f"noise must be [{B},{self.A}]")
         self.rng_counter += 1
+        if self.float_actions and given is not None and given.numel() != B * self.A:
+            raise RuntimeError(f"actions must be [{B},{self.A}], got {tuple(given.shape)}")
+        if self.dist_kind == "bern":
+            call("ppo_heads_bern_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), self.A, ptr(noise), self.rng_seed, self.rng_counter,
+                 int(bool(deterministic)),
+                 ptr(given.reshape(-1).contiguous() if given is not None else None, torch.float32, "action"),
+                 value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
+                 ptr(logp), ptr(ent), stream())
+            return value, action, logp, ent
         if self.gauss:
-            if given is not None and given.numel() != B * self.A:
-                raise RuntimeError(f"actions must be [{B},{self.A}], got {tuple(given.shape)}")
             call("ppo_heads_gauss_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
                  self.pv(self.WA), self.pv(self.BA), self.pv(self.LS), self.A, ptr(noise), self.rng_seed,
                  self.rng_counter, int(bool(deterministic)),
@@ -349,9 +361,21 @@ class CNNEngine:
         part_b = ws.get("part_b", nblk * (1 + (2 * A if self.gauss else A)), device=dev)
         part_l = ws.get("part_l", nblk * 4, device=dev)
         inv_b = 1.0 / B
+        if self.float_actions and storage.actions.shape[-1] != A:
+            raise RuntimeError(f"storage holds {storage.actions.shape[-1]} action dimensions, the policy {A}")
+        if self.dist_kind == "bern":
+            # dist.linear's gradients: Categorical's partial layouts, summed by ppo_heads_reduce
+            call("ppo_heads_bern_train", feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), A, idx.data_ptr(), 0,
+                 ptr(storage.actions, torch.float32, "storage.actions"), storage.action_log_probs.data_ptr(),
+                 adv.data_ptr(), storage.value_preds.data_ptr(), storage.returns.data_ptr(), hp["clip"],
+                 hp["value_coef"], hp["entropy_coef"], inv_b, int(hp["use_clipped_value_loss"]), int(feat_act),
+                 dfeat.data_ptr(), ptr(dfeat_v), part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), s)
+            call("ppo_heads_reduce", part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), nblk, H, A,
+                 self.gv(self.WC), self.gv(self.BC), self.gv(self.WA), self.gv(self.BA), loss_acc.data_ptr(), inv_b,
+                 1.0, int(hp["use_clipped_value_loss"]), s)
+            return
         if self.gauss:
-            if storage.actions.shape[-1] != A:
-                raise RuntimeError(f"storage holds {storage.actions.shape[-1]} action dimensions, the policy {A}")
             call("ppo_heads_gauss_train", feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC), self.pv(self.BC),
                  self.pv(self.WA), self.pv(self.BA), self.pv(self.LS), A, idx.data_ptr(), 0,
                  ptr(storage.actions, torch.float32, "storage.actions"), storage.action_log_probs.data_ptr(),
@@ -567,8 +591,8 @@ class RecurrentEngine(CNNEngine):
             self.status[2].zero_()
             raise RuntimeError("evaluate_actions: the persistent GRU kernel timed out (its outputs are invalid; "
                                "ppo_gru_persist_set(0) selects the per-step launches)")
-        value, _, logp, ent = self._heads(hout, R, want_entropy=True,
-                                          given=action.to(self.device, torch.float32 if self.gauss else torch.int64))
+        given = action.to(self.device, torch.float32 if self.float_actions else torch.int64)
+        value, _, logp, ent = self._heads(hout, R, want_entropy=True, given=given)
         return value, logp, ent, hout[(T - 1) * N:]
 
     @_with_precision

@@ -118,6 +118,11 @@ SIGNATURES = {
     "ppo_heads_gauss_train": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_p, c_p,
                               c_p, c_f, c_f, c_f, c_f, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "ppo_heads_gauss_reduce": [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_d, c_f, c_p],
+    # heads_bern.hip (its partials go through ppo_heads_reduce)
+    "ppo_heads_bern_act": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ull, c_ull, c_int, c_p, c_p, c_p,
+                           c_p, c_p, c_p],
+    "ppo_heads_bern_train": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_p, c_p, c_p,
+                             c_f, c_f, c_f, c_f, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     # obs.hip
     "ppo_obs_preprocess": [c_p, c_ll, c_int, c_int, c_int, c_p, c_d, c_int, c_p, c_ll, c_p],
     "ppo_frame_stack": [c_p, c_int, c_int, c_ll, c_p, c_p, c_int, c_p],

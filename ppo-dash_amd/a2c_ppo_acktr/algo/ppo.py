@@ -131,7 +131,8 @@ class PPO():
         advantages = rollouts.normalized_advantages()            # ppo.py:35-37
         if self._loss_acc is None or self._loss_acc.device != eng.device:
             # {value loss, action loss, entropy} sums, the count of stored actions outside
-            # [0, A) (Box: of rows with a non-finite stored action), and (filled at the
+            # [0, A) (Box: of rows with a non-finite stored action; MultiBinary: of rows with
+            # a component that is not 0 or 1), and (filled at the
             # end) the persistent-GRU timeout flag
             self._loss_acc = torch.zeros(5, dtype=torch.float64, device=eng.device)
         else:
@@ -200,6 +201,10 @@ class PPO():
             # Box: a NaN / inf action makes every gradient of its minibatch non-finite
             raise ValueError("PPO.update: {:.0f} non-finite stored action(s) in the rollout".format(
                 acc[3] * _dist.world_size() / self.ppo_epoch))
+        if acc[3] > 0 and getattr(eng, "dist_kind", "cat") == "bern":
+            # MultiBinary: torch's Bernoulli.log_prob raises ValueError for a value outside {0, 1}
+            raise ValueError("PPO.update: {:.0f} stored action(s) with a component that is not 0 or 1 in the "
+                             "rollout".format(acc[3] * _dist.world_size() / self.ppo_epoch))
         if acc[3] > 0:
             # the reference's log_probs gather (distributions.py:22) raises on such an index, before
             # its optimizer step; each epoch visits every stored row once, hence / ppo_epoch

@@ -39,7 +39,10 @@ def set_sampling_mode(mode):
     generator — the draw torch.multinomial makes on the reference CPU path — so a
     seeded run consumes the host generator exactly like the reference does.  A Box
     policy draws standard normal noise instead: Box-Muller on the counter RNG, or
-    torch.empty(N, A).normal_() (torch.normal's draw) in 'host' mode."""
+    torch.empty(N, A).normal_() (torch.normal's draw) in 'host' mode.  A MultiBinary
+    policy draws uniforms in [0, 1) and sets action = (u < p): 24-bit uniforms from
+    the counter RNG, or torch.empty(N, A).uniform_() in 'host' mode, which is the
+    draw torch.bernoulli(probs) makes on the CPU (FixedBernoulli.sample)."""
     if mode not in ("device", "host"):
         raise ValueError(mode)
     _SAMPLING["mode"] = mode
@@ -133,9 +136,6 @@ class Policy(nn.Module):
 
     def hip_engine(self, device=None):
         require_device()
-        if not isinstance(self.dist, (Categorical, DiagGaussian)):
-            raise NotImplementedError("MultiBinary action spaces do not run on the MI355X engine "
-                                      "(Discrete and Box do)")
         if device is None:
             p = next(self.parameters())
             device = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -155,13 +155,16 @@ class Policy(nn.Module):
             if isinstance(self.dist, DiagGaussian):
                 # torch.normal(mean, std)'s draw on the reference CPU path (FixedNormal.sample)
                 return torch.empty(n, self.dist.fc_mean.weight.shape[0]).normal_()
+            if isinstance(self.dist, Bernoulli):
+                # torch.bernoulli(probs)'s draw on the reference CPU path (FixedBernoulli.sample)
+                return torch.empty(n, self.dist.linear.weight.shape[0]).uniform_()
             return torch.empty(n, self.dist.linear.weight.shape[0]).exponential_(1)
         return None
 
     # ----------------------------------------------------------------- API
     def act(self, visual_inputs, vector_inputs, rnn_hxs, masks, deterministic=False):
-        """model.py:54-66 -> (value [N,1], action [N,1] int64 (Box: [N,A] float), action_log_probs [N,1],
-        rnn_hxs)."""
+        """model.py:54-66 -> (value [N,1], action [N,1] int64 (Box: [N,A] float; MultiBinary: [N,A] float
+        holding 0.0 / 1.0), action_log_probs [N,1], rnn_hxs)."""
         eng = self.hip_engine()
         n = visual_inputs.shape[0]
         noise = None if deterministic else self._noise(n)
@@ -189,7 +192,7 @@ class Policy(nn.Module):
     def evaluate_actions(self, visual_inputs, vector_inputs, rnn_hxs, masks, action):
         """model.py:72-79 -> (value [B,1], action_log_probs [B,1], dist_entropy (0-d), rnn_hxs)."""
         eng = self.hip_engine()
-        action = action.to(eng.device, torch.float32 if eng.gauss else torch.int64)
+        action = action.to(eng.device, torch.float32 if eng.float_actions else torch.int64)
         if self.is_recurrent:
             if visual_inputs.shape[0] == rnn_hxs.shape[0]:   # model.py:112 single-step branch
                 value, _, logp, ent, rnn_hxs = eng.act(visual_inputs, given=action, want_entropy=True,

@@ -31,6 +31,15 @@ class Box(object):
         self.shape = tuple(shape)
 
 
+class MultiBinary(object):
+    """duck-typed gym.spaces.MultiBinary (storage.py:24, model.py:36): n binary
+    components, actions are float [n] vectors holding 0.0 / 1.0"""
+
+    def __init__(self, n):
+        self.n = int(n)
+        self.shape = (self.n,)
+
+
 class SyntheticVecEnv(object):
     def __init__(self, num_envs, obs_shape=(4, 84, 84), num_actions=8, seed=123, p_done=0.01, device=None):
         self.num_envs = num_envs

@@ -1,0 +1,576 @@
+// Actor-critic heads for MultiBinary action spaces: Bernoulli distribution and the
+// PPO loss (the third sibling of heads.hip and heads_gauss.hip).
+//
+// Reference:
+//   Bernoulli (linear -> FixedBernoulli(logits))  distributions.py:93-104
+//   FixedBernoulli log_probs / entropy / mode  distributions.py:45-56
+//     (torch Bernoulli(logits=z): probs = sigmoid(z), sample = bernoulli(probs)
+//      = (u < probs) for u ~ U[0, 1), log_prob = -BCEWithLogits(z, a) summed over
+//      the A dims, entropy = BCEWithLogits(z, probs) summed, mode = probs > 0.5)
+//   Policy.act / evaluate_actions  model.py:54-79
+//   PPO clipped surrogate + clipped value loss + entropy  algo/ppo.py:61-81
+//
+// Same layout as heads.hip: one wave per row, HW waves per block, lane l holds
+// hidden columns l + 64c, the 1 + A head dot products are wave-reduced so every
+// lane holds value and the A logits z_o.  With e = exp(-|z|):
+//   softplus(-|z|) = log1p(e),  p = sigmoid(z) = z >= 0 ? 1/(1+e) : e/(1+e)
+//   log_prob = Σ_o a_o z_o - max(z_o, 0) - log1p(e_o)
+//   entropy  = Σ_o log1p(e_o) + |z_o| e_o/(1+e_o)
+// both finite for any finite z.
+//
+// Training gradients (g_logp = dL/dlog_prob of the row, as in heads.hip):
+//   dL/dz_o = g_logp (a_o - p_o) + (entropy_coef / B) z_o p_o (1 - p_o)
+// The parameters are dist.linear, so the partial layouts are heads.hip's and
+// ppo_heads_reduce sums them.
+#include "heads_common.h"
+#include "tune.h"
+
+namespace {
+
+// per-dimension terms of Bernoulli(logits = z)
+struct BernT {
+  float p;     // sigmoid(z); for z >= 0 this is torch's 1 / (1 + exp(-z)) operation for operation
+  float small; // sigmoid(-|z|) = min(p, 1 - p)
+  float sp;    // softplus(-|z|) = log1p(exp(-|z|))
+  float ent;   // entropy of the dimension
+};
+
+__device__ __forceinline__ BernT bern_terms(float z) {
+  const float az = fabsf(z);
+  const float e = expf(-az);
+  const float inv = 1.f / (1.f + e);
+  const float small = e * inv;   // sigmoid(-|z|)
+  BernT t;
+  t.p = z >= 0.f ? inv : small;
+  t.small = small;
+  t.sp = log1pf(e);
+  t.ent = t.sp + az * small;
+  return t;
+}
+
+// one uniform in [0, 1) per (row, dimension) from the counter RNG: the top 24 bits
+// of the hash heads_gauss.hip feeds to Box-Muller
+__device__ __forceinline__ float uniform_noise(uint64_t seed, uint64_t counter, long long row, int o, int A) {
+  const uint64_t h = mix64(seed ^ mix64(counter * 0x2545F4914F6CDD1Dull + (uint64_t)(row * A + o)));
+  return (float)((uint32_t)(h >> 40)) * (1.0f / 16777216.0f);
+}
+
+struct ActArgs {
+  const float *feat, *feat_v;
+  int N, H, A;
+  const float *wc, *bc, *wa, *ba;
+  const float* noise;      // [N][A] uniform draws in [0, 1) (host replay) or NULL
+  unsigned long long seed, counter;
+  int deterministic;
+  const float* given;      // [N][A] actions to evaluate or NULL
+  float *value, *action, *logp, *entropy;
+  int rows_per_wave;
+};
+
+// act / evaluate: value, action (sample | mode | given), log_prob, entropy
+// FAST: A == AMAX, H == 64·HC, no separate critic features (compile-time bounds)
+template <int HC, int AMAX, bool FAST>
+__global__ __launch_bounds__(64 * HW) void bern_act_kernel(const ActArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int H = FAST ? 64 * HC : a.H, A = FAST ? AMAX : a.A;
+  const float* const feat_v = FAST ? nullptr : a.feat_v;
+  HeadW<HC, AMAX> w;
+  load_head_w(w, a.wc, a.wa, A, H, lane);
+  const float b0 = a.bc[0];
+  const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
+  for (int rr = 0; rr < a.rows_per_wave; ++rr) {
+    const long long row = r0 + rr;
+    if (row >= a.N) break;
+    float f[HC], fv[HC];
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+      const bool in = lane + 64 * c < H;
+      f[c] = in ? a.feat[row * H + lane + 64 * c] : 0.f;
+      fv[c] = feat_v ? (in ? feat_v[row * H + lane + 64 * c] : 0.f) : f[c];
+    }
+    float value, z[AMAX], act[AMAX];
+    head_dots(w, f, fv, value, z, b0, a.ba, A);
+    float lp = 0.f, ent = 0.f;
+#pragma unroll
+    for (int o = 0; o < AMAX; ++o) {
+      act[o] = 0.f;
+      if (o < A) {
+        const BernT t = bern_terms(z[o]);
+        if (a.given) {
+          act[o] = a.given[row * A + o];
+        } else if (a.deterministic) {
+          act[o] = t.p > 0.5f ? 1.f : 0.f;   // torch.gt(probs, 0.5): p == 0.5 gives 0
+        } else {
+          const float u = a.noise ? a.noise[row * A + o] : uniform_noise(a.seed, a.counter, row, o, A);
+          act[o] = u < t.p ? 1.f : 0.f;
+        }
+        lp += act[o] * z[o] - fmaxf(z[o], 0.f) - t.sp;
+        ent += t.ent;
+      }
+    }
+    if (lane == 0) {
+      if (a.value) a.value[row] = value;
+      if (a.logp) a.logp[row] = lp;
+      if (a.entropy) a.entropy[row] = ent;
+    }
+    if (a.action && lane < A) {
+      float v = 0.f;   // act[lane] as a sum of one term and zeros (see bern_row)
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o) v += lane == o ? act[o] : 0.f;
+      a.action[row * A + lane] = v;
+    }
+  }
+}
+
+struct BernTrainArgs {
+  const float* feat;       // [B][H] policy features
+  const float* feat_v;     // [B][H] critic features (MLPBase) or NULL (= feat)
+  int B, H, A;
+  const float *wc, *bc, *wa, *ba;
+  const int64_t* idx;      // storage row of each sample (nullable: row0 + b)
+  long long row0;
+  const float* actions;    // storage plane [row][A]
+  const float *old_logp, *adv, *vpred, *ret;
+  float clip, value_coef, entropy_coef, inv_b;
+  int use_clipped_value_loss;
+  int feat_act;            // activation producing the features: 0 none (GRU), 1 ReLU, 2 tanh
+  float* dfeat;            // [B][H]
+  float* dfeat_v;          // [B][H] critic-branch gradient (MLPBase) or NULL
+  float* part_w;           // [blocks][1+A][H]: critic, logits
+  float* part_b;           // [blocks][1+A]: critic bias, logit biases
+  float* part_loss;        // [blocks][4]: Σ max(l1,l2), Σ min(s1,s2), Σ H, # rows with a component not 0 or 1
+  int rows_per_wave;
+};
+
+// per-row storage scalars, lane j holding row r0 + j of the wave (see heads.hip)
+struct RowScalars {
+  float adv = 0.f, olp = 0.f, vo = 0.f, ret = 0.f;
+  int sr_lo = 0, sr_hi = 0;   // storage row (the action plane is read per row, one row ahead)
+  __device__ __forceinline__ void load(const BernTrainArgs& a, long long r0, int lane) {
+    if (lane < a.rows_per_wave && r0 + lane < a.B) {
+      const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
+      sr_lo = (int)(sr & 0xffffffffll);
+      sr_hi = (int)(sr >> 32);
+      adv = a.adv[sr];
+      olp = a.old_logp[sr];
+      vo = a.vpred[sr];
+      ret = a.ret[sr];
+    }
+  }
+  __device__ __forceinline__ long long storage_row(int j) const {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane(sr_lo, j);
+    const long long hi = __builtin_amdgcn_readlane(sr_hi, j);
+    return (hi << 32) | (long long)lo;
+  }
+};
+
+__device__ __forceinline__ float bcast(float x, int j) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
+}
+
+// Loss terms and head gradients of one row.  The per-dimension terms (one expf, one
+// log1pf and one division each) are computed once, by lane o for dimension o: that
+// lane already holds the row's a_o.  The sums over o and the A gradients are then
+// read lane by lane in ascending o, so every lane ends up with the same values; the
+// ratio / clip / surrogate and the value loss are exactly heads_train_kernel's.
+template <int AMAX>
+__device__ __forceinline__ void bern_row(const BernTrainArgs& a, int A, int lane, float value,
+                                         const float (&z)[AMAX], float acur, float adv, float olp, float vo, float R,
+                                         float& g_v, float (&gz)[AMAX], float& s_vl, float& s_al, float& s_ent,
+                                         float& s_bad) {
+  const float clip = a.clip;
+  const float ec = a.entropy_coef * a.inv_b;
+  // this lane's logit (lanes >= A: 0, their results are never read).  A sum of one
+  // term and zeros, not a chain of selects: the compiler turns such a chain into a
+  // lane-indexed load from a scratch copy of z
+  float zl = 0.f;
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o) zl += (o < A && lane == o) ? z[o] : 0.f;
+  const float al = lane < A ? acur : 0.f;
+  const bool bad = __builtin_amdgcn_ballot_w64(lane < A && !(al == 0.f || al == 1.f)) != 0;   // NaN included
+  const BernT t = bern_terms(zl);
+  const float lpl = al * zl - fmaxf(zl, 0.f) - t.sp;
+  float lp = 0.f, ent = 0.f;
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o) {
+    if (o < A) {
+      lp += bcast(lpl, o);
+      ent += bcast(t.ent, o);
+    }
+  }
+  s_bad += bad ? 1.f : 0.f;   // counted; PPO.update raises
+  s_ent += ent;
+  // action loss (ppo.py:61-66)
+  const float ratio = expf(lp - olp);
+  const float surr1 = ratio * adv;
+  const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
+  const float surr2 = rc * adv;
+  const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
+  const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
+  const float g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+  // value loss (ppo.py:68-77)
+  float vl_row;
+  if (a.use_clipped_value_loss) {
+    const float dv = value - vo;
+    const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
+    const float l1 = (value - R) * (value - R);
+    const float l2 = (vpc - R) * (vpc - R);
+    vl_row = fmaxf(l1, l2);
+    const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
+    const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
+    g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+  } else {
+    vl_row = (R - value) * (R - value);
+    g_v = a.value_coef * a.inv_b * (value - R);
+  }
+  s_vl += vl_row;
+  s_al += fminf(surr1, surr2);
+  // p and p (1 - p) from sigmoid(-|z|), without cancellation
+  const float amp = zl >= 0.f ? (al - 1.f) + t.small : al - t.small;   // a_o - p_o
+  const float gzl = g_logp * amp + ec * zl * (t.small * (1.f - t.small));
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o) gz[o] = o < A ? bcast(gzl, o) : 0.f;
+}
+
+// head-bias / loss partials of the block: redb[wave] = {gbc, gba[AMAX], Σvl, Σal,
+// Σent, #bad} summed over the HW waves in a fixed order (heads.hip's part_b layout)
+template <int AMAX>
+__device__ __forceinline__ void bern_store_scalars(const BernTrainArgs& a, int A, float (&redb)[HW][AMAX + 5],
+                                                   int lane, int wave, float gbc, const float (&gba)[AMAX],
+                                                   float s_vl, float s_al, float s_ent, float s_bad) {
+  if (lane == 0) {
+    redb[wave][0] = gbc;
+#pragma unroll
+    for (int o = 0; o < AMAX; ++o) redb[wave][1 + o] = gba[o];
+    redb[wave][AMAX + 1] = s_vl;
+    redb[wave][AMAX + 2] = s_al;
+    redb[wave][AMAX + 3] = s_ent;
+    redb[wave][AMAX + 4] = s_bad;
+  }
+  __syncthreads();
+  const int t = threadIdx.x, NO = 1 + A;
+  if (t < NO) {
+    float s = 0.f;
+    for (int q = 0; q < HW; ++q) s += redb[q][t];
+    a.part_b[(size_t)blockIdx.x * NO + t] = s;
+  }
+  if (t < 4) {
+    float s = 0.f;
+    for (int q = 0; q < HW; ++q) s += redb[q][AMAX + 1 + t];
+    a.part_loss[(size_t)blockIdx.x * 4 + t] = s;
+  }
+}
+
+// FAST: A == AMAX, H == 64·HC, no separate critic features / gradient
+template <int HC, int AMAX, bool FAST>
+__global__ __launch_bounds__(64 * HW) void bern_train_kernel(const BernTrainArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int H = FAST ? 64 * HC : a.H, A = FAST ? AMAX : a.A;
+  const float* const feat_v = FAST ? nullptr : a.feat_v;
+  float* const dfeat_v = FAST ? nullptr : a.dfeat_v;
+  HeadW<HC, AMAX> w;
+  load_head_w(w, a.wc, a.wa, A, H, lane);
+  const float b0 = a.bc[0];
+  float gwc[HC], gwa[AMAX][HC], gbc = 0.f, gba[AMAX];
+#pragma unroll
+  for (int c = 0; c < HC; ++c) gwc[c] = 0.f;
+#pragma unroll
+  for (int o = 0; o < AMAX; ++o) {
+    gba[o] = 0.f;
+#pragma unroll
+    for (int c = 0; c < HC; ++c) gwa[o][c] = 0.f;
+  }
+  float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
+  const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
+  RowScalars q;
+  q.load(a, r0, lane);
+  // features and the row's A action floats (lane o holds dimension o) one row ahead
+  float fn[HC], fvn[HC], an = 0.f;
+  auto load_row = [&](int rr) {
+    const long long row = r0 + rr;
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+      const bool in = row < a.B && lane + 64 * c < H;
+      fn[c] = in ? a.feat[row * H + lane + 64 * c] : 0.f;
+      fvn[c] = feat_v ? (in ? feat_v[row * H + lane + 64 * c] : 0.f) : fn[c];
+    }
+    if (row < a.B) {
+      const long long sr = q.storage_row(rr);
+      if (lane < A) an = a.actions[sr * A + lane];
+    }
+  };
+  load_row(0);
+  for (int rr = 0; rr < a.rows_per_wave; ++rr) {
+    const long long row = r0 + rr;
+    if (row >= a.B) break;
+    float f[HC], fv[HC];
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+      f[c] = fn[c];
+      fv[c] = fvn[c];
+    }
+    const float acur = an;
+    if (rr + 1 < a.rows_per_wave) load_row(rr + 1);
+    float value, z[AMAX];
+    head_dots(w, f, fv, value, z, b0, a.ba, A);
+    float g_v, gz[AMAX];
+    bern_row(a, A, lane, value, z, acur, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g_v, gz,
+             s_vl, s_al, s_ent, s_bad);
+    // dL/dh for this lane's columns, through the features' activation; head grads
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+      const float dv = g_v * w.wc[c];
+      float d = dfeat_v ? 0.f : dv;
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o) d += gz[o] * w.wa[o][c];
+      if (lane + 64 * c < H) {
+        const size_t p = (size_t)row * H + lane + 64 * c;
+        a.dfeat[p] = act_grad(d, f[c], a.feat_act);
+        if (dfeat_v) dfeat_v[p] = act_grad(dv, fv[c], a.feat_act);
+      }
+      gwc[c] += g_v * fv[c];
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o) gwa[o][c] += gz[o] * f[c];
+    }
+    gbc += g_v;
+#pragma unroll
+    for (int o = 0; o < AMAX; ++o) gba[o] += gz[o];
+  }
+  // block reduction of the head-gradient partials across the HW waves
+  __shared__ float red[HW][64 * HC];
+  __shared__ float redb[HW][AMAX + 5];
+  const int NO = 1 + A;
+  for (int o = 0; o < NO; ++o) {
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+      float v = gwc[c];
+#pragma unroll
+      for (int p = 0; p < AMAX; ++p)
+        if (o == p + 1) v = gwa[p][c];
+      red[wave][lane + 64 * c] = v;
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int c = 0; c < HC; ++c) {
+        const int j = lane + 64 * c;
+        float s = red[0][j];
+        for (int p = 1; p < HW; ++p) s += red[p][j];
+        if (j < H) a.part_w[((size_t)blockIdx.x * NO + o) * H + j] = s;
+      }
+    }
+    __syncthreads();
+  }
+  bern_store_scalars<AMAX>(a, A, redb, lane, wave, gbc, gba, s_vl, s_al, s_ent, s_bad);
+}
+
+// bern_train_kernel at H = 512, A = 8 (the FAST case) with the head weights in
+// LDS, as heads_train_lds_kernel: a lane holds the columns 4·lane + q + 256·c2 and
+// reads the 9 weight rows of those columns as ds_read_b128.  The register version
+// keeps 72 weight VGPRs next to 72 gradient accumulators (one wave per SIMD).
+__global__ __launch_bounds__(64 * HW) void bern_train_lds_kernel(const BernTrainArgs a) {
+  constexpr int A = 8, H = 512;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ f32x4 Wl[9][128];   // row 0: critic, rows 1..8: logits
+  for (int i = threadIdx.x; i < 9 * H; i += 64 * HW) {
+    const int o = i / H, k = i - H * o;
+    reinterpret_cast<float*>(&Wl[o][0])[k] = o == 0 ? a.wc[k] : a.wa[(o - 1) * H + k];
+  }
+  const float b0 = a.bc[0];
+  float ba[A];
+#pragma unroll
+  for (int o = 0; o < A; ++o) ba[o] = a.ba[o];
+  __syncthreads();
+  f32x4 gw[9][2];   // Σ_rows g_o · f (o = 0: critic), this lane's columns
+#pragma unroll
+  for (int o = 0; o < 9; ++o) gw[o][0] = gw[o][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float gbc = 0.f, gba[A];
+#pragma unroll
+  for (int o = 0; o < A; ++o) gba[o] = 0.f;
+  float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
+  const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
+  RowScalars q;
+  q.load(a, r0, lane);
+  f32x4 fn[2];
+  float an = 0.f;
+  auto load_row = [&](int rr) {
+    const long long row = r0 + rr;
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2)
+      fn[c2] = row < a.B ? reinterpret_cast<const f32x4*>(a.feat + row * H)[lane + 64 * c2] : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (row < a.B) {
+      const long long sr = q.storage_row(rr);
+      if (lane < A) an = a.actions[sr * A + lane];
+    }
+  };
+  load_row(0);
+  for (int rr = 0; rr < a.rows_per_wave; ++rr) {
+    const long long row = r0 + rr;
+    if (row >= a.B) break;
+    const f32x4 f[2] = {fn[0], fn[1]};
+    const float acur = an;
+    if (rr + 1 < a.rows_per_wave) load_row(rr + 1);
+    float dots[9];
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+      float t = 0.f;
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        const f32x4 w = Wl[o][lane + 64 * c2];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) t += f[c2][p] * w[p];
+      }
+      dots[o] = wave_sum(t);
+    }
+    const float value = dots[0] + b0;
+    float z[A];
+#pragma unroll
+    for (int o = 0; o < A; ++o) z[o] = dots[1 + o] + ba[o];
+    float g[9], gz[A];   // g[0] = dL/dvalue, g[1 + o] = dL/dz_o
+    bern_row(a, A, lane, value, z, acur, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g[0], gz,
+             s_vl, s_al, s_ent, s_bad);
+#pragma unroll
+    for (int o = 0; o < A; ++o) g[1 + o] = gz[o];
+    // dL/dfeature of this lane's columns (through the activation), head gradients
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      f32x4 d = Wl[0][lane + 64 * c2] * g[0];
+#pragma unroll
+      for (int o = 1; o < 9; ++o) {
+        const f32x4 w = Wl[o][lane + 64 * c2];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) d[p] += g[o] * w[p];
+      }
+      f32x4 y;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) y[p] = act_grad(d[p], f[c2][p], a.feat_act);
+      reinterpret_cast<f32x4*>(a.dfeat + row * H)[lane + 64 * c2] = y;
+#pragma unroll
+      for (int o = 0; o < 9; ++o)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) gw[o][c2][p] += g[o] * f[c2][p];
+    }
+    gbc += g[0];
+#pragma unroll
+    for (int o = 0; o < A; ++o) gba[o] += gz[o];
+  }
+  // block reduction of the head-gradient partials across the HW waves (fixed order)
+  __shared__ f32x4 red[HW][128];
+  __shared__ float redb[HW][A + 5];
+  for (int o = 0; o < 9; ++o) {
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) red[wave][lane + 64 * c2] = gw[o][c2];
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        f32x4 t = red[0][lane + 64 * c2];
+        for (int p = 1; p < HW; ++p) t += red[p][lane + 64 * c2];
+        reinterpret_cast<f32x4*>(a.part_w + ((size_t)blockIdx.x * 9 + o) * H)[lane + 64 * c2] = t;
+      }
+    }
+    __syncthreads();
+  }
+  bern_store_scalars<A>(a, A, redb, lane, wave, gbc, gba, s_vl, s_al, s_ent, s_bad);
+}
+
+template <int HC, int AMAX>
+int launch_act(const ActArgs& a, hipStream_t st) {
+  const unsigned blocks = ceil_div(a.N, HW * a.rows_per_wave);
+  if (a.A == AMAX && a.H == 64 * HC && !a.feat_v)
+    bern_act_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(a);
+  else
+    bern_act_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(a);
+  PPO_LAUNCH_CHECK("bern_act_kernel");
+  return 0;
+}
+
+template <int AMAX>
+int dispatch_act(int HC, const ActArgs& a, hipStream_t st) {
+  switch (HC) {
+    case 1: return launch_act<1, AMAX>(a, st);
+    case 2: return launch_act<2, AMAX>(a, st);
+    case 4: return launch_act<4, AMAX>(a, st);
+    case 8: return launch_act<8, AMAX>(a, st);
+  }
+  ppo_set_error("heads: hidden size %d not supported (<= 512)", a.H);
+  return PPO_EARG;
+}
+
+template <int HC, int AMAX>
+int launch_train(const BernTrainArgs& a, int blocks, hipStream_t st) {
+  if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
+      ((uintptr_t)a.feat & 15) == 0 && ((uintptr_t)a.dfeat & 15) == 0 && ((uintptr_t)a.part_w & 15) == 0) {
+    bern_train_lds_kernel<<<blocks, 64 * HW, 0, st>>>(a);
+    PPO_LAUNCH_CHECK("bern_train_lds_kernel");
+    return 0;
+  }
+  if (a.A == AMAX && a.H == 64 * HC && !a.feat_v && !a.dfeat_v)
+    bern_train_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(a);
+  else
+    bern_train_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(a);
+  PPO_LAUNCH_CHECK("bern_train_kernel");
+  return 0;
+}
+
+template <int AMAX>
+int dispatch_train(int HC, const BernTrainArgs& a, int blocks, hipStream_t st) {
+  switch (HC) {
+    case 1: return launch_train<1, AMAX>(a, blocks, st);
+    case 2: return launch_train<2, AMAX>(a, blocks, st);
+    case 4: return launch_train<4, AMAX>(a, blocks, st);
+    case 8: return launch_train<8, AMAX>(a, blocks, st);
+  }
+  ppo_set_error("heads: hidden size %d not supported (<= 512)", a.H);
+  return PPO_EARG;
+}
+
+}  // namespace
+
+// Policy.act / get_value / evaluate_actions heads for FixedBernoulli(logits):
+//   given   != NULL: log_prob / entropy of the given [N][A] actions
+//   deterministic: action = (sigmoid(z) > 0.5)
+//   noise   != NULL: action = (noise < sigmoid(z)), noise uniform in [0, 1) (host-replay parity mode)
+//   noise   == NULL: 24-bit uniforms from the counter RNG (seed, counter, row, o)
+PPO_API int ppo_heads_bern_act(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                               const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+                               unsigned long long counter, int deterministic, const float* given, float* value,
+                               float* action, float* logp, float* entropy, void* stream) {
+  PPO_REQUIRE(N >= 0 && A >= 1 && A <= 16, "ppo_heads_bern_act: N=%d A=%d (1..16 action dimensions)", N, A);
+  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_bern_act: hidden size %d (1..512)", H);
+  ProfScope prof("heads_bern_act", as_stream(stream), (double)N * (4.0 * H * (feat_v ? 2 : 1) + 12.0 + 4.0 * A));
+  if (N == 0) return 0;
+  ActArgs a;
+  a.feat = feat; a.feat_v = feat_v; a.N = N; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
+  a.noise = noise; a.seed = seed; a.counter = counter; a.deterministic = deterministic;
+  a.given = given; a.value = value; a.action = action; a.logp = logp; a.entropy = entropy;
+  // as ppo_heads_act: ~4096 waves in flight, one row per wave at a rollout batch of 4,096
+  a.rows_per_wave = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(N, 4096)));
+  if (A <= 8) return dispatch_act<8>(hc_of(H), a, as_stream(stream));
+  return dispatch_act<16>(hc_of(H), a, as_stream(stream));
+}
+
+// the Bernoulli ppo_heads_train: same launch shape (ppo_heads_train_blocks) and the
+// same partial layouts, float actions [row][A]; ppo_heads_reduce sums the partials
+PPO_API int ppo_heads_bern_train(const float* feat, const float* feat_v, int B, int H, const float* wc,
+                                 const float* bc, const float* wa, const float* ba, int A, const int64_t* idx,
+                                 long long row0, const float* actions, const float* old_logp, const float* adv,
+                                 const float* vpred, const float* ret, float clip, float value_coef,
+                                 float entropy_coef, float inv_b, int use_clipped_value_loss, int feat_act,
+                                 float* dfeat, float* dfeat_v, float* part_w, float* part_b, float* part_loss,
+                                 void* stream) {
+  PPO_REQUIRE(B > 0 && A >= 1 && A <= 16, "ppo_heads_bern_train: B=%d A=%d", B, A);
+  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_bern_train: hidden size %d (1..512)", H);
+  ProfScope prof("heads_bern_train", as_stream(stream),
+                 (double)B * (8.0 * H * (feat_v ? 2 : 1) + (idx ? 8.0 : 0.0) + 24.0 + 4.0 * A));
+  BernTrainArgs a;
+  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
+  a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = old_logp; a.adv = adv;
+  a.vpred = vpred; a.ret = ret; a.clip = clip; a.value_coef = value_coef; a.entropy_coef = entropy_coef;
+  a.inv_b = inv_b; a.use_clipped_value_loss = use_clipped_value_loss; a.feat_act = feat_act;
+  a.dfeat = dfeat; a.dfeat_v = dfeat_v; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
+  a.rows_per_wave = 32;
+  const int blocks = ppo_heads_train_blocks(B);
+  if (A <= 8) return dispatch_train<8>(hc_of(H), a, blocks, as_stream(stream));
+  return dispatch_train<16>(hc_of(H), a, blocks, as_stream(stream));
+}

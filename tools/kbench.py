@@ -123,9 +123,21 @@ def main():
              0.5, 0.01, 1.0 / B, 1, 1, dz3.data_ptr(), None, part_g.data_ptr(), part_g.data_ptr() + 4 * nb * 9 * H,
              part_g.data_ptr() + 4 * nb * (9 * H + 17), s)
 
+    # the MultiBinary counterpart: float 0 / 1 actions [rows][8], Categorical's partial layout
+    st_actb = (torch.rand(rows, 8, device=dev, generator=g) < 0.5).float()
+
+    def heads_bern_train():
+        nb = call("ppo_heads_train_blocks", B)
+        call("ppo_heads_bern_train", h.data_ptr(), None, B, H, hw.data_ptr(), hw.data_ptr() + 4 * H,
+             hw.data_ptr() + 4 * (H + 1), hw.data_ptr() + 4 * (9 * H + 1), 8, idx.data_ptr(), 0, st_actb.data_ptr(),
+             st_f[0].data_ptr(), st_f[1].data_ptr(), st_f[2].data_ptr(), st_f[3].data_ptr(), 0.1, 0.5, 0.01, 1.0 / B, 1,
+             1, dz3.data_ptr(), None, part.data_ptr(), part.data_ptr() + 4 * nb * 9 * H,
+             part.data_ptr() + 4 * nb * (9 * H + 9), s)
+
     K = {
         "heads_train": (heads_train, 0.0),
         "heads_gauss_train": (heads_gauss_train, 0.0),
+        "heads_bern_train": (heads_bern_train, 0.0),
         "conv1_fwd": (lambda: call("ppo_conv1_fwd", obs.data_ptr(), 1, idx.data_ptr(), 0, 4, B, w1.data_ptr(),
                                    b1.data_ptr(), a1.data_ptr(), s), 2.0 * B * 400 * 32 * 256),
         "conv2_fwd": (lambda: call("ppo_conv2_fwd", a1.data_ptr(), B, pk[0], b2.data_ptr(), a2.data_ptr(), s),
