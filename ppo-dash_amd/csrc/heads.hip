@@ -52,6 +52,13 @@ __device__ __forceinline__ void categorical(const float (&z)[AMAX], int A, float
   for (int o = 0; o < AMAX; ++o) p[o] = p[o] / s2;
 }
 
+// A stored / given action as an index: the range is decided on the 64-bit value
+// (2^32 + 2 must not pass as 2); anything outside [0, A) becomes -1, which no
+// later `(unsigned)act < (unsigned)A` or `o == act` accepts.
+__device__ __forceinline__ int action_index(int64_t v, int A) {
+  return (uint64_t)v < (uint64_t)A ? (int)v : -1;
+}
+
 __device__ __forceinline__ float exp_noise(uint64_t seed, uint64_t counter, long long row, int o, int A) {
   const uint64_t h = mix64(seed ^ mix64(counter * 0x2545F4914F6CDD1Dull + (uint64_t)(row * A + o)));
   return -logf(u01_open0(h));
@@ -89,7 +96,7 @@ __global__ __launch_bounds__(64 * HW) void heads_act_kernel(
     categorical(z, A, nl, p);
     int act;
     if (given) {
-      act = (int)given[row];
+      act = action_index(given[row], A);
     } else {
       act = 0;
       float best = -INFINITY;
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
   float q_adv = 0.f, q_olp = 0.f, q_vo = 0.f, q_ret = 0.f;
   if (lane < a.rows_per_wave && r0 + lane < a.B) {
     const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
-    q_act = (int)a.actions[sr];
+    q_act = action_index(a.actions[sr], A);
     q_adv = a.adv[sr];
     q_olp = a.old_logp[sr];
     q_vo = a.vpred[sr];
@@ -347,7 +354,7 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
   float q_adv = 0.f, q_olp = 0.f, q_vo = 0.f, q_ret = 0.f;
   if (lane < a.rows_per_wave && r0 + lane < a.B) {
     const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
-    q_act = (int)a.actions[sr];
+    q_act = action_index(a.actions[sr], A);
     q_adv = a.adv[sr];
     q_olp = a.old_logp[sr];
     q_vo = a.vpred[sr];

@@ -59,7 +59,7 @@ SATURATED = (512, 8, 130, "idx", False, 1)   # run with logit weights scaled for
 
 
 @functools.lru_cache(maxsize=None)
-def _kernel_case(H, A, B, rows, sep_v, feat_act, zscale=4.0):
+def _kernel_case(H, A, B, rows, sep_v, feat_act, zscale=4.0, use_clipped=True):
     """fp32 inputs (random features in [-1, 1], logit weights scaled so the logits'
     standard deviation is zscale / 3: |z| <~ 4 at the default, actions drawn from
     those logits) and the float64 reference computed from those same fp32 values;
@@ -90,7 +90,7 @@ def _kernel_case(H, A, B, rows, sep_v, feat_act, zscale=4.0):
     planes["vpred"][sr] = f32(value + g.normal(size=B) * 0.2)
     c.update(planes, actions=act, R=Rn)
     r = R.bern_loss_head_grads(value, z, act[sr], planes["old_logp"][sr], planes["adv"][sr], planes["vpred"][sr],
-                               planes["ret"][sr], CLIP, VC, EC)
+                               planes["ret"][sr], CLIP, VC, EC, use_clipped)
     ag = (lambda dd, y: dd) if feat_act == 0 else (lambda dd, y: dd * (y > 0)) if feat_act == 1 else \
         (lambda dd, y: dd * (1 - y * y))
     dv = r["g_value"][:, None] * d(c["wc"])[None, :]
@@ -111,7 +111,7 @@ def _kernel_case(H, A, B, rows, sep_v, feat_act, zscale=4.0):
     return c
 
 
-def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act):
+def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped=True):
     Hh = _hip()
     t = {k: _dev(c[k]) for k in ("feat", "wc", "bc", "wa", "ba", "actions", "old_logp", "adv", "vpred", "ret")}
     fv = _dev(c["feat_v"]) if sep_v else None
@@ -125,7 +125,8 @@ def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act):
     p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     Hh.call("ppo_heads_bern_train", p(t["feat"]), p(fv), B, H, p(t["wc"]), p(t["bc"]), p(t["wa"]), p(t["ba"]), A,
             p(idx), 0 if rows == "idx" else rows, p(t["actions"]), p(t["old_logp"]), p(t["adv"]), p(t["vpred"]),
-            p(t["ret"]), CLIP, VC, EC, 1.0 / B, 1, feat_act, p(out["dfeat"]), p(out["dfeat_v"]), p(out["part_w"]),
+            p(t["ret"]), CLIP, VC, EC, 1.0 / B, int(use_clipped), feat_act, p(out["dfeat"]),
+            p(out["dfeat_v"]), p(out["part_w"]),
             p(out["part_b"]), p(out["part_l"]), _s())
     torch.cuda.synchronize()
     return t, out, nblk
@@ -178,9 +179,13 @@ def test_bern_train_kernel_vs_float64(gpu, H, A, B, rows, sep_v, feat_act):
     vs the float64 helper, max |err| <= 1e-5 * max(max|ref|, 1e-3) per tensor
     (test_mlp_minibatch_grads_vs_oracle's rule); losses rtol 2e-5, atol 1e-6; no bad
     action counted; a second identical launch gives bit-identical partials."""
-    c = _kernel_case(H, A, B, rows, sep_v, feat_act)
-    t, out, nblk = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act)
-    _, out2, _ = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act)
+    _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, True)
+
+
+def _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, use_clipped):
+    c = _kernel_case(H, A, B, rows, sep_v, feat_act, use_clipped=use_clipped)
+    t, out, nblk = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped)
+    _, out2, _ = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped)
     for k in ("part_w", "part_b", "part_l", "dfeat"):
         assert torch.equal(out[k], out2[k]), k
     assert not torch.isnan(out["part_w"]).any() and not torch.isnan(out["part_b"]).any()
@@ -197,6 +202,20 @@ def test_bern_train_kernel_vs_float64(gpu, H, A, B, rows, sep_v, feat_act):
         print(f"{name}: max err {err:.3e} bound {bound:.3e}")
         assert err <= bound, (name, err, bound)
     np.testing.assert_allclose(acc.cpu().numpy()[:3], ref["losses"], rtol=2e-5, atol=1e-6)
+    return c
+
+
+@pytest.mark.parametrize("H,A,B,rows,sep_v,feat_act", [KERNEL_CASES[2], KERNEL_CASES[6]])
+def test_bern_train_kernel_unclipped_value_loss(gpu, H, A, B, rows, sep_v, feat_act):
+    """test_bern_train_kernel_vs_float64 with use_clipped_value_loss = 0 (value loss
+    0.5 mean((R - v)^2)) on the generic (100, 8, 129) and the LDS-weight (512, 8, 130)
+    case: the same bounds against the float64 helper's unclipped branch, whose
+    critic gradients differ from the clipped branch's on these inputs."""
+    c = _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, False)
+    clipped = _kernel_case(H, A, B, rows, sep_v, feat_act)["ref"]
+    gap = np.abs(clipped["g_wc"] - c["ref"]["g_wc"]).max()
+    assert gap > 100 * 1e-5 * np.abs(c["ref"]["g_wc"]).max(), gap
+    assert abs(clipped["losses"][0] - c["ref"]["losses"][0]) > 1e-3 * c["ref"]["losses"][0]
 
 
 @pytest.mark.parametrize("lds", [1, 0])

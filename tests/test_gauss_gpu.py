@@ -58,7 +58,7 @@ KERNEL_CASES = [
 
 
 @functools.lru_cache(maxsize=None)
-def _kernel_case(H, A, B, rows, sep_v, feat_act):
+def _kernel_case(H, A, B, rows, sep_v, feat_act, use_clipped=True):
     """fp32 inputs (random features in [-1, 1], weights scaled so |mu| <~ 2, logstd in
     [-1, 0.5], actions within 3 sigma of the mean) and the float64 reference computed
     from those same fp32 values; computed once per case, never modified."""
@@ -89,7 +89,7 @@ def _kernel_case(H, A, B, rows, sep_v, feat_act):
     planes["vpred"][sr] = f32(value + g.normal(size=B) * 0.2)
     c.update(planes, actions=act, R=R)
     r = G.gauss_loss_head_grads(value, mean, c["logstd"], act[sr], planes["old_logp"][sr], planes["adv"][sr],
-                                planes["vpred"][sr], planes["ret"][sr], CLIP, VC, EC)
+                                planes["vpred"][sr], planes["ret"][sr], CLIP, VC, EC, use_clipped)
     ag = (lambda dd, y: dd) if feat_act == 0 else (lambda dd, y: dd * (y > 0)) if feat_act == 1 else \
         (lambda dd, y: dd * (1 - y * y))
     dv = r["g_value"][:, None] * d(c["wc"])[None, :]
@@ -110,7 +110,7 @@ def _kernel_case(H, A, B, rows, sep_v, feat_act):
     return c
 
 
-def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act):
+def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped=True):
     Hh = _hip()
     t = {k: _dev(c[k]) for k in ("feat", "wc", "bc", "wa", "ba", "logstd", "actions", "old_logp", "adv", "vpred",
                                  "ret")}
@@ -125,8 +125,8 @@ def _run_train(gpu, c, H, A, B, rows, sep_v, feat_act):
     p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     Hh.call("ppo_heads_gauss_train", p(t["feat"]), p(fv), B, H, p(t["wc"]), p(t["bc"]), p(t["wa"]), p(t["ba"]),
             p(t["logstd"]), A, p(idx), 0 if rows == "idx" else rows, p(t["actions"]), p(t["old_logp"]), p(t["adv"]),
-            p(t["vpred"]), p(t["ret"]), CLIP, VC, EC, 1.0 / B, 1, feat_act, p(out["dfeat"]), p(out["dfeat_v"]),
-            p(out["part_w"]), p(out["part_b"]), p(out["part_l"]), _s())
+            p(t["vpred"]), p(t["ret"]), CLIP, VC, EC, 1.0 / B, int(use_clipped), feat_act, p(out["dfeat"]),
+            p(out["dfeat_v"]), p(out["part_w"]), p(out["part_b"]), p(out["part_l"]), _s())
     torch.cuda.synchronize()
     return t, out, nblk
 
@@ -164,10 +164,14 @@ def test_gauss_train_kernel_vs_float64(gpu, H, A, B, rows, sep_v, feat_act):
     logstd gradients vs the float64 helper, max |err| <= 1e-5 * max(max|ref|, 1e-3)
     per tensor (test_mlp_minibatch_grads_vs_oracle's rule); losses rtol 2e-5, atol
     1e-6; a second identical launch gives bit-identical partials."""
+    _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, True)
+
+
+def _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, use_clipped):
     Hh = _hip()
-    c = _kernel_case(H, A, B, rows, sep_v, feat_act)
-    t, out, nblk = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act)
-    _, out2, _ = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act)
+    c = _kernel_case(H, A, B, rows, sep_v, feat_act, use_clipped)
+    t, out, nblk = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped)
+    _, out2, _ = _run_train(gpu, c, H, A, B, rows, sep_v, feat_act, use_clipped)
     for k in ("part_w", "part_b", "part_l", "dfeat"):
         assert torch.equal(out[k], out2[k]), k
     assert not torch.isnan(out["part_w"]).any() and not torch.isnan(out["part_b"]).any()
@@ -190,6 +194,20 @@ def test_gauss_train_kernel_vs_float64(gpu, H, A, B, rows, sep_v, feat_act):
         print(f"{name}: max err {err:.3e} bound {bound:.3e}")
         assert err <= bound, (name, err, bound)
     np.testing.assert_allclose(acc.cpu().numpy()[:3], ref["losses"], rtol=2e-5, atol=1e-6)
+    return c
+
+
+@pytest.mark.parametrize("H,A,B,rows,sep_v,feat_act", [KERNEL_CASES[2], KERNEL_CASES[6]])
+def test_gauss_train_kernel_unclipped_value_loss(gpu, H, A, B, rows, sep_v, feat_act):
+    """test_gauss_train_kernel_vs_float64 with use_clipped_value_loss = 0 (value loss
+    0.5 mean((R - v)^2)) on the generic (100, 8, 129) and the LDS-weight (512, 8, 130)
+    case: the same bounds against the float64 helper's unclipped branch, whose
+    critic gradients differ from the clipped branch's on these inputs."""
+    c = _train_vs_float64(gpu, H, A, B, rows, sep_v, feat_act, False)
+    clipped = _kernel_case(H, A, B, rows, sep_v, feat_act)["ref"]
+    gap = np.abs(clipped["g_wc"] - c["ref"]["g_wc"]).max()
+    assert gap > 100 * 1e-5 * np.abs(c["ref"]["g_wc"]).max(), gap
+    assert abs(clipped["losses"][0] - c["ref"]["losses"][0]) > 1e-3 * c["ref"]["losses"][0]
 
 
 # ------------------------------------------------------------------- sampling
