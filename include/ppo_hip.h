@@ -249,6 +249,9 @@ int ppo_colsum(const float* src, long long ld, int rows, long long cols, float* 
  *   "fc_splitk_tile" 1 that fc on 128 x 128 tiles with 16-B slab stores (default), 0 on
  *                 128 x 64 tiles (bit-identical results for the same slice count)
  *   "rgb_aff"     1 affine-folded raw RGB conv1 (default), 0 bit-exact decode
+ *   "conv3_dgrad_group" 1 ppo_conv3_dgrad_bits on tiles of 16 images for B >= 16 (default; only
+ *                 the valid taps are issued), 0 the per-image kernel everywhere (bit-identical
+ *                 results; ppo_conv3_dgrad always runs the per-image kernel)
  *   "stagger"     schedule bits 0..15 (default 2; every value gives the same results);
  *                 larger values are refused (they select timing-anatomy paths that give
  *                 wrong results by design, accepted only by a -DPPO_DIAG build)

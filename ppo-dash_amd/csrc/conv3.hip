@@ -21,11 +21,11 @@ namespace {
 // row tiles 3 (w >> 2) .. +2.
 // BITS: the a2 ReLU mask comes as bits (a2 points at u64 words [B][81] from
 // ppo_conv2_fwd_mask: 648 B instead of 20.7 KB per image).
-template <int NP, bool BITS = false>
-__global__ __launch_bounds__(512) void conv3_dgrad_x9_kernel(const float* __restrict__ dz3, int B,
-                                                            const uint16_t* __restrict__ wpl,
-                                                            const float* __restrict__ a2,
-                                                            float* __restrict__ dz2, int stagger) {
+template <int NP, bool BITS>
+__device__ __forceinline__ void conv3_dgrad_img_body(const float* __restrict__ dz3, int B,
+                                                     const uint16_t* __restrict__ wpl,
+                                                     const float* __restrict__ a2, float* __restrict__ dz2,
+                                                     int stagger) {
   constexpr int GW = 25, CS = 288, PLU = 4 * CS, KS = 9, WN = 64 * 288;
   constexpr int DU = 49 * 4, MC = 81 * 64 / 4, MPER = (MC + 511) / 512;
   __shared__ __attribute__((aligned(16))) uint16_t S[2][3 * PLU * 8];
@@ -172,6 +172,145 @@ __global__ __launch_bounds__(512) void conv3_dgrad_x9_kernel(const float* __rest
     __syncthreads();   // every wave is done with stage cur; stage cur ^ 1 is complete
     cur ^= 1;
   }
+}
+
+// conv3 dgrad on 16-image tiles (knob conv3_dgrad_group, the mask-bits form, B >= 16):
+// a tile is input pixel (y, x) of the 16 consecutive images of a group, MFMA column
+// i16 = image b0 + i16, so every row of a tile has the same valid taps and only the
+// 441 valid (pixel, tap) pairs are issued — 662 MFMAs per image at 6 products instead
+// of 960, and the taps the per-image kernel issues against its zero border add exact
+// zeros, so the two kernels agree bit for bit: per output element the taps in
+// ascending s = 3 ky + kx, the part products in PPO_PRODUCTS order.
+// One persistent block (8 waves) per CU walks groups.  The LDS holds one stage: the
+// group's dz3 split into three bf16 planes, 16-B unit (plane, co chunk c, pixel, image)
+// at plane * 3136 + c * 784 + pixel * 16 + image (no border: every unit is real;
+// 150,528 B) and the 16 images' mask words (10,368 B).  A fragment read's 16 lanes
+// of one g are the 16 images of one (c, pixel): 16 consecutive units, conflict-free
+// (tools/conv3_group_banks.py); the address is the lane's base plus an immediate.
+// The next group's dz3 (7 units per lane) and mask words wait in registers during
+// the compute and are split and written between the two barriers of the group
+// boundary.  Wave w: ci tile w & 3 (weights as in the per-image kernel), output rows
+// {0, 1, 2, 3, 8} (w < 4: 10 of the 21 valid (y, ky)) or {4 .. 7} (11) — both halves
+// of a ci tile on one SIMD.  Per (y, ky) the 7 source pixels are read once each,
+// ox = 6 .. 0, and feed outputs x = ox + kx, which keeps every output's kx ascending.
+// A ragged last group: the missing images load zeros and their stores are dropped,
+// both by the range of the group's buffer resources.
+template <int NP>
+__device__ __forceinline__ void conv3_dgrad_group_body(const float* __restrict__ dz3, int B,
+                                                       const uint16_t* __restrict__ wpl,
+                                                       const uint64_t* __restrict__ m2,
+                                                       float* __restrict__ dz2) {
+  constexpr int KS = 9, WN = 64 * 288, GI = 16;
+  constexpr int CSU = 49 * GI, PLU = 4 * CSU;   // 16-B units per co chunk, per plane
+  constexpr int MW = GI * 81, MPER = (MW + 511) / 512, NJ = 7;   // px = wave + 8 j, j < NJ
+  __shared__ __attribute__((aligned(16))) uint16_t S[3 * PLU * 8];
+  __shared__ __attribute__((aligned(16))) uint32_t Mk[2 * MW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
+  const int nt = wave & 3, mh = wave >> 2, ci = 16 * nt + i16;
+  bf16x8 bw[KS][3];
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+      bw[s][p] = *reinterpret_cast<const bf16x8*>(wpl + (size_t)p * WN + ci * 288 + 32 * s + 8 * g);
+  wait_vm0();
+  f32x4 stg[NJ][2];
+  uint2 mbv[MPER];
+  // lane (i16, g) of wave w fetches co chunk g of pixels w, w + 8, .. of image b0 + i16
+  // (a wave's load covers 16 whole 128-B pixel rows); images and mask words past the
+  // batch are out of the resources' range and read 0
+  auto fetch = [&](int b0) {
+    const int n = max(min(B - b0, GI), 0);
+    const auto rd = make_rsrc(dz3 + (size_t)b0 * 1568, n * 6272);
+    const auto rm = make_rsrc(m2 + (size_t)b0 * 81, n * 648);
+    const int o = i16 * 6272 + wave * 128 + g * 32;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int off = wave + 8 * j < 49 ? o + 1024 * j : 0x7fffffc0;
+      stg[j][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, off, 0, 0));
+      stg[j][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, off + 16, 0, 0));
+    }
+#pragma unroll
+    for (int k = 0; k < MPER; ++k)
+      mbv[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rm, 8 * (tid + 512 * k), 0, 0));
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int px = wave + 8 * j;
+      if (px < 49) {
+        const int q = g * CSU + px * GI + i16;
+        Frag3 f;
+        split8(stg[j][0], stg[j][1], f, false);
+        *reinterpret_cast<bf16x8*>(&S[8 * q]) = f.h;
+        *reinterpret_cast<bf16x8*>(&S[8 * (PLU + q)]) = f.m;
+        *reinterpret_cast<bf16x8*>(&S[8 * (2 * PLU + q)]) = f.l;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < MPER; ++k)
+      if (tid + 512 * k < MW) reinterpret_cast<uint2*>(Mk)[tid + 512 * k] = mbv[k];
+  };
+  const int step = GI * gridDim.x, c0 = 16 * nt + 4 * g;
+  const int ny = mh ? 4 : 5;
+  int b0 = GI * blockIdx.x;
+  if (b0 < B) fetch(b0);
+  for (; b0 < B; b0 += step) {
+    put();
+    fetch(b0 + step);
+    __syncthreads();   // the group's stage is complete
+    const auto rs = make_rsrc(dz2 + (size_t)b0 * 5184, min(B - b0, GI) * 20736);
+    for (int iy = 0; iy < ny; ++iy) {
+      const int y = mh ? 4 + iy : (iy < 4 ? iy : 8);
+      f32x4 acc[9];
+#pragma unroll
+      for (int x = 0; x < 9; ++x) acc[x] = zero4();
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const int oy = y - ky;
+        if (oy < 0 || oy > 6) continue;   // wave-uniform
+        const uint16_t* row = S + 8 * (g * CSU + 7 * GI * oy + i16);
+        const Frag3 w[3] = {{bw[3 * ky][0], bw[3 * ky][1], bw[3 * ky][2]},
+                            {bw[3 * ky + 1][0], bw[3 * ky + 1][1], bw[3 * ky + 1][2]},
+                            {bw[3 * ky + 2][0], bw[3 * ky + 2][1], bw[3 * ky + 2][2]}};
+#pragma unroll
+        for (int ox = 6; ox >= 0; --ox) {
+          const uint16_t* q = row + 8 * GI * ox;
+          Frag3 a;
+          a.h = *reinterpret_cast<const bf16x8*>(q);
+          a.m = *reinterpret_cast<const bf16x8*>(q + 8 * PLU);
+          a.l = *reinterpret_cast<const bf16x8*>(q + 16 * PLU);
+#define PPO_PART(X, Y) \
+  _Pragma("unroll") for (int kx = 0; kx < 3; ++kx) acc[ox + kx] = mma(w[kx].Y, a.X, acc[ox + kx]);
+          PPO_PRODUCTS(NP, PPO_PART)
+#undef PPO_PART
+        }
+      }
+      // epilogue: lane (i16, g) holds channels c0 .. c0 + 3 of pixel (y, x) of image
+      // b0 + i16 — one 16-B store per pixel, masked by that image's m2 word
+#pragma unroll
+      for (int x = 0; x < 9; ++x) {
+        const int m = 9 * y + x;
+        const uint32_t mw = Mk[i16 * 162 + 2 * m + (c0 >> 5)] >> (c0 & 31);
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = ((mw >> r) & 1u) != 0 ? acc[x][r] : 0.f;
+        bstore_f32x4(o, rs, i16 * 20736 + 4 * (m * 64 + c0));
+      }
+    }
+    __syncthreads();   // every wave is done with the stage
+  }
+}
+
+// GRP: the 16-image-tile form (BITS only)
+template <int NP, bool BITS = false, bool GRP = false>
+__global__ __launch_bounds__(512) void conv3_dgrad_x9_kernel(const float* __restrict__ dz3, int B,
+                                                            const uint16_t* __restrict__ wpl,
+                                                            const float* __restrict__ a2,
+                                                            float* __restrict__ dz2, int stagger) {
+  static_assert(BITS || !GRP, "the group form reads mask bits");
+  if constexpr (GRP) conv3_dgrad_group_body<NP>(dz3, B, wpl, reinterpret_cast<const uint64_t*>(a2), dz2);
+  else conv3_dgrad_img_body<NP, BITS>(dz3, B, wpl, a2, dz2, stagger);
 }
 
 // standalone conv3 forward: 12 waves, the lone output in the same launch
@@ -383,14 +522,24 @@ PPO_API int ppo_conv3_fwd_mask(const float* a2, int B, const float* w3p, const f
 template <bool BITS>
 static int conv3_dgrad_img(const float* dz3, int B, const float* w3d, const float* mask, float* dz2, void* stream) {
   if (B <= 0) return 0;
-  const unsigned nb = img_grid(B);
   int slot;
   const bool prof = ppo_prof_begin("conv3_dgrad", as_stream(stream), &slot);
   const uint16_t* wpl = planes_of(w3d, 64 * 288);
   const int sg = tune_stagger(), np = tune_products();
-  if (np == 9) conv3_dgrad_x9_kernel<9, BITS><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
-  else if (np == 1) conv3_dgrad_x9_kernel<1, BITS><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
-  else conv3_dgrad_x9_kernel<6, BITS><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
+  auto go = [&](auto GRP) {
+    constexpr bool G = decltype(GRP)::value;
+    const unsigned nb = img_grid(G ? (B + 15) / 16 : B);   // G: a block walks groups of 16 images
+    if (np == 9) conv3_dgrad_x9_kernel<9, BITS, G><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
+    else if (np == 1) conv3_dgrad_x9_kernel<1, BITS, G><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
+    else conv3_dgrad_x9_kernel<6, BITS, G><<<nb, 512, 0, as_stream(stream)>>>(dz3, B, wpl, mask, dz2, sg);
+  };
+  // the fp32 mask of 16 images does not fit the LDS beside their dz3: bits only
+  bool grp = false;
+  if constexpr (BITS) {
+    grp = B >= 16 && tune_key(TK_CONV3_DGRAD_GROUP) != 0;
+    if (grp) go(std::true_type{});
+  }
+  if (!grp) go(std::false_type{});
   if (prof) ppo_prof_end(slot, as_stream(stream), 2.0 * B * 49 * 32 * 576);
   PPO_LAUNCH_CHECK("conv3_dgrad_x9_kernel");
   return 0;

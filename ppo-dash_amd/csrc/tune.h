@@ -2,7 +2,8 @@
 // launchers of every other file read it through these accessors.
 #pragma once
 
-enum { TK_CONV1_FWD, TK_CONV1_WGRAD, TK_X9, TK_FC_SPLITK, TK_RGB_AFF, TK_FC_SPLITK_TILE, TK_N };
+enum { TK_CONV1_FWD, TK_CONV1_WGRAD, TK_X9, TK_FC_SPLITK, TK_RGB_AFF, TK_FC_SPLITK_TILE,
+       TK_CONV3_DGRAD_GROUP, TK_N };
 
 int tune_key(int k);      // value of knob TK_*
 int tune_products();      // split products per operand pair: 1, 6 or 9

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--B", type=int, default=65536)
     ap.add_argument("--H", type=int, default=512)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=1, help="passes over the selected kernels (interleaved A/B)")
     ap.add_argument("--only", default="")
     ap.add_argument("--tune", default="", help="key=v[,key=v...] tile variants (ppo_tune_set)")
     ap.add_argument("--z2", type=int, default=0, help="conv2 wgrad split count (default: ppo_wgrad_splits)")
@@ -134,6 +135,13 @@ def main():
              1, dz3.data_ptr(), None, part.data_ptr(), part.data_ptr() + 4 * nb * 9 * H,
              part.data_ptr() + 4 * nb * (9 * H + 9), s)
 
+    def conv3_dgrad_bits(group):
+        """the knob position for this launch only (the engine's default is restored)"""
+        keep = call("ppo_tune_get", b"conv3_dgrad_group")
+        call("ppo_tune_set", b"conv3_dgrad_group", group)
+        call("ppo_conv3_dgrad_bits", dz3.data_ptr(), B, pk[4], m2.data_ptr(), dz2.data_ptr(), s)
+        call("ppo_tune_set", b"conv3_dgrad_group", keep)
+
     K = {
         "heads_train": (heads_train, 0.0),
         "heads_gauss_train": (heads_gauss_train, 0.0),
@@ -189,6 +197,9 @@ def main():
                                         m2.data_ptr(), s), 2.0 * B * 81 * 64 * 512),
         "conv3_dgrad_bits": (lambda: call("ppo_conv3_dgrad_bits", dz3.data_ptr(), B, pk[4], m2.data_ptr(),
                                           dz2.data_ptr(), s), 2.0 * B * 49 * 32 * 576),
+        # the two forms of conv3 dgrad side by side: per image (knob conv3_dgrad_group = 0), 16-image tiles (1)
+        "conv3_dgrad_bits_g0": (lambda: conv3_dgrad_bits(0), 2.0 * B * 49 * 32 * 576),
+        "conv3_dgrad_bits_g1": (lambda: conv3_dgrad_bits(1), 2.0 * B * 49 * 32 * 576),
         "conv2_dgrad_bits": (lambda: call("ppo_conv2_dgrad_bits", dz2.data_ptr(), B, pk[5], m1.data_ptr(),
                                           dz1.data_ptr(), s), 2.0 * B * 81 * 64 * 512),
         "conv2_wgrad": (lambda: call("ppo_conv2_wgrad", dz2.data_ptr(), a1.data_ptr(), B, z2, slab.data_ptr(),
@@ -229,20 +240,21 @@ def main():
         "conv1_fwd_mask", "conv2_fwd_mask", "conv3_fwd_mask", "fc_fwd", "fc_dgrad_bits", "fc_wgrad", "conv3_dgrad_bits",
         "conv3_wgrad", "conv2_dgrad_bits", "conv2_wgrad", "conv1_wgrad", "conv1_fwd", "conv2_fwd", "trunk_4096"]
     total = 0.0
-    for name, (fn, fl) in K.items():
-        if only and name not in only:
-            continue
-        fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
+    for rnd in range(a.rounds):
+        for name, (fn, fl) in K.items():
+            if only and name not in only:
+                continue
             fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / a.reps
-        total += ms
-        tf = fl / (ms * 1e-3) / 1e12 if fl else 0.0
-        print(f"{name:14s} {ms:8.3f} ms  {tf:7.1f} TFLOP/s", flush=True)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / a.reps
+            total += ms / a.rounds
+            tf = fl / (ms * 1e-3) / 1e12 if fl else 0.0
+            print(f"{name:14s} {ms:8.3f} ms  {tf:7.1f} TFLOP/s", flush=True)
     print(f"{'total':14s} {total:8.3f} ms")
 
 
