@@ -189,6 +189,14 @@ int ppo_linear_fwd_ex(const float* x, const int64_t* idx, int M, int K, int lda,
 /* dgrad through the activation that produced `act` (mode 1 ReLU, 2 tanh) */
 int ppo_linear_dgrad_ex(const float* dy, int M, int K, const float* wt, int N, const float* act, int ldact, int mode,
                         float* dx, void* stream);
+/* model.py:231-232 hidden_critic = critic(x), hidden_actor = actor(x): the gradient both
+ * towers send into their common input (the GRU output of a recurrent MLPBase),
+ *   dx[m][n] = Σ_{k<K0} dy0[m][k]·wt0[n][k] + Σ_{k<K1} dy1[m][k]·wt1[n][k]
+ * in one launch with one accumulator per element: pair 0's k range first, then pair
+ * 1's (deterministic).  No activation factor.  K0, K1 positive multiples of 4, else
+ * PPO_EARG; nothing is stored past row M. */
+int ppo_linear_dgrad_pair(const float* dy0, const float* wt0, int K0, const float* dy1, const float* wt1, int K1,
+                          int M, int N, float* dx, void* stream);
 /* dst [cols][rows] = srcᵀ */
 int ppo_transpose(const float* src, int rows, int cols, float* dst, void* stream);
 /* algo/ppo.py:80-81 loss.backward() through the trunk: dgrad with the ReLU mask

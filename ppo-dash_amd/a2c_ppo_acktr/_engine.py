@@ -2,6 +2,8 @@
 
 CNNEngine        CNNBase, feed-forward (model.py:169-199)
 RecurrentEngine  CNNBase + [vector obs] + GRU (model.py:89-166, 192-199)
+MLPEngine           MLPBase, feed-forward (model.py:202-234)
+RecurrentMLPEngine  MLPBase + GRU in front of the towers (model.py:111-166, 224-234)
 
 Each owns the flat parameter / gradient buffers (every nn.Parameter of the
 Policy is re-pointed to a view of one contiguous fp32 buffer, so clip + Adam is
@@ -653,15 +655,19 @@ class MLPEngine(CNNEngine):
 
     def __init__(self, policy, device):   # noqa: D401 — own init, shares the CNNEngine machinery
         base = policy.base
-        if base.is_recurrent:
-            raise NotImplementedError("recurrent MLPBase is not on the HIP path")
+        if base.is_recurrent != self.recurrent:
+            raise NotImplementedError("a recurrent MLPBase runs on RecurrentMLPEngine, a feed-forward one on "
+                                      "MLPEngine (Policy.hip_engine() selects the engine)")
         self.policy, self.device = policy, device
         self.H = base._hidden_size
-        self.I = base.actor[0].weight.shape[1]
+        # x = cat(obs, vector_obs) feeds the GRU of a recurrent base, else the towers' first layers
+        self.I = (base.gru.weight_ih_l0 if self.recurrent else base.actor[0].weight).shape[1]
         self.V = base.vector_obs_len
         self.obs_dim = self.I - self.V
         self.Ip = (self.I + 3) // 4 * 4
         self._bind_dist(policy)
+        if self.recurrent and (self.H % 32 != 0 or self.H > 512 or self.I < 1):
+            raise NotImplementedError("GRU engine needs hidden_size a multiple of 32 (<= 512)")
         if self.H % 4 != 0 or self.H > 512:
             raise NotImplementedError(f"MLPBase hidden_size {self.H}: multiples of 4 up to 512")
         self.params = list(policy.parameters())
@@ -702,11 +708,16 @@ class MLPEngine(CNNEngine):
                  self.Ip - self.obs_dim, s)
         return x
 
+    def _tower_in(self):
+        """(width of the towers' input rows, actor.0 weight, critic.0 weight)"""
+        return self.Ip, self.aw1, self.cw1
+
     def towers(self, x, B, ws):
-        dev, H, Ip, s = self.device, self.H, self.Ip, stream()
+        dev, H, s = self.device, self.H, stream()
+        Ip, aw1, cw1 = self._tower_in()
         out = {}
-        for name, w1, b1, w2, b2 in (("a", self.aw1, self.AB1, self.AW2, self.AB2),
-                                     ("c", self.cw1, self.CB1, self.CW2, self.CB2)):
+        for name, w1, b1, w2, b2 in (("a", aw1, self.AB1, self.AW2, self.AB2),
+                                     ("c", cw1, self.CB1, self.CW2, self.CB2)):
             h1 = ws.get(name + "1", B * H, device=dev)
             h2 = ws.get(name + "2", B * H, device=dev)
             call("ppo_linear_fwd_ex", x.data_ptr(), None, B, Ip, Ip, w1, self.pv(b1), H, h1.data_ptr(), H, 2, s)
@@ -741,11 +752,176 @@ class MLPEngine(CNNEngine):
         dc2 = ws.get("dc2", B * H, device=dev)
         self._heads_train(storage, adv, idx, t["a"][1], B, hp, loss_acc, da2, feat_act=2, feat_v=t["c"][1],
                           dfeat_v=dc2)
+        self._towers_backward(t, x, B, da2, dc2, self.Ip, 3, self.I)
+        self._finish_step(optimizer)
+
+    def _towers_backward(self, t, x, B, da2, dc2, K, kind, width):
+        """Weight gradients of both towers from dL/d(second-layer pre-activations); the first
+        layers read x [B][K] (kind / width: ppo_wgrad_reduce's column map).  Returns
+        dL/d(first-layer pre-activations) of the actor and the critic tower."""
+        ws, dev, H = self.ws["train"], self.device, self.H
+        d1s = []
         for name, d2, w1, b1, w2, b2, w2T in (("a", da2, self.AW1, self.AB1, self.AW2, self.AB2, self.aw2T),
                                                ("c", dc2, self.CW1, self.CB1, self.CW2, self.CB2, self.cw2T)):
             h1 = t[name][0]
             self._dense_wgrad(d2, h1, B, H, H, 0, 0, w2, b2)
             d1 = ws.get("d1" + name, B * H, device=dev)
             call("ppo_linear_dgrad_ex", d2.data_ptr(), B, H, w2T, H, h1.data_ptr(), H, 2, d1.data_ptr(), stream())
-            self._dense_wgrad(d1, x, B, H, self.Ip, 3, self.I, w1, b1)
+            self._dense_wgrad(d1, x, B, H, K, kind, width, w1, b1)
+            d1s.append(d1)
+        return d1s
+
+
+class RecurrentMLPEngine(MLPEngine):
+    """MLPBase(recurrent=True) (model.py:111-166, 224-234): x = cat(obs, vector_obs) -> GRU ->
+    actor / critic towers on the GRU output (their first layers are H x H) -> heads.
+    Parameter order: gru.{weight_ih, weight_hh, bias_ih, bias_hh}, actor.0, actor.2, critic.0,
+    critic.2, critic_linear, dist.  The GRU input is the observation, so nothing flows back
+    past W_ih; dL/d(GRU output) is the two towers' gradient in one ppo_linear_dgrad_pair."""
+
+    GIH, GHH, GBI, GBH = range(4)
+    AW1, AB1, AW2, AB2, CW1, CB1, CW2, CB2, WC, BC, WA, BA, LS = range(4, 17)
+    recurrent = True
+
+    def pack(self, force=False):
+        key = (sum(p._version for p in self.params), self.epoch)
+        if not force and self.packed is not None and key == self._pack_key:
+            return
+        H, Ip, s = self.H, self.Ip, stream()
+        if self.packed is None:
+            self.packed = torch.empty(3 * H * Ip + 3 * H * H + 4 * H * H, device=self.device)
+        b = self.packed.data_ptr()
+        self.wih_pad, self.whhT = b, b + 4 * 3 * H * Ip
+        self.aw1T = self.whhT + 4 * 3 * H * H
+        self.cw1T, self.aw2T, self.cw2T = (self.aw1T + 4 * H * H * i for i in (1, 2, 3))
+        # W_ih zero-padded to Ip inputs; ppo_gru_pack's W_ih[:, :H]ᵀ plane is not built: the GRU
+        # input gets no gradient here (and I < H is the usual case)
+        call("ppo_concat_cols", self.pv(self.GIH), None, 3 * H, self.I, self.wih_pad, Ip, 0, Ip, s)
+        call("ppo_transpose", self.pv(self.GHH), 3 * H, H, self.whhT, s)
+        for w, dst in ((self.AW1, self.aw1T), (self.CW1, self.cw1T), (self.AW2, self.aw2T), (self.CW2, self.cw2T)):
+            call("ppo_transpose", self.pv(w), H, H, dst, s)
+        self._pack_key = key
+
+    def _tower_in(self):
+        return self.H, self.pv(self.AW1), self.pv(self.CW1)
+
+    def _rows(self, obs, vec, R):
+        """host-facing arguments -> fp32 device rows [R][obs_dim], [R][V] | None"""
+        obs = (obs if obs.is_cuda else obs.to(self.device)).to(torch.float32).reshape(R, -1).contiguous()
+        if obs.shape[1] != self.obs_dim:
+            raise RuntimeError(f"MLPBase expects [N,{self.obs_dim}] observations, got {tuple(obs.shape)}")
+        v = vec.to(self.device, torch.float32).reshape(R, self.V).contiguous() if self.V else None
+        return obs, v
+
+    def _gi(self, x, B, ws):
+        """gi [B][3H] = x_pad · W_ihᵀ + b_ih"""
+        gi = ws.get("gi", B * 3 * self.H, device=self.device)
+        call("ppo_linear_fwd_ex", x.data_ptr(), None, B, self.Ip, self.Ip, self.wih_pad, self.pv(self.GBI),
+             3 * self.H, gi.data_ptr(), 3 * self.H, 0, stream())
+        return gi
+
+    @_with_precision
+    def act(self, obs, deterministic=False, noise=None, given=None, want_entropy=False, value_only=False,
+            vec=None, hxs=None, masks=None):
+        """Single step (model.py:112-115): returns (value, action, logp, entropy, hxs')."""
+        self.ensure_bound()
+        self.pack()
+        B = obs.shape[0]
+        obs, v = self._rows(obs, vec, B)
+        ws = self.ws[self.act_ws]
+        gi = self._gi(self._x(obs, v, None, B, ws), B, ws)
+        hxs = hxs.to(self.device, torch.float32).reshape(B, self.H).contiguous()
+        m = masks.to(self.device, torch.float32).reshape(B).contiguous() if masks is not None else None
+        hout = torch.empty(B, self.H, device=self.device)
+        call("ppo_gru_step_fwd", hxs.data_ptr(), ptr(m), None, self.pv(self.GHH), self.pv(self.GBH), gi.data_ptr(),
+             B, self.H, hout.data_ptr(), None, None, None, None, None, stream())
+        t = self.towers(hout, B, ws)
+        value, action, logp, ent = self._heads(t["a"][1], B, deterministic, noise, given, want_entropy, value_only,
+                                               hv=t["c"][1])
+        return value, action, logp, ent, hout
+
+    @_with_precision
+    def evaluate_sequence(self, obs, vec, hxs, masks, action):
+        """Multi-step branch (model.py:116-165): rows are t*N + n."""
+        self.ensure_bound()
+        self.pack()
+        R, N = obs.shape[0], hxs.shape[0]
+        T = R // N
+        obs, v = self._rows(obs, vec, R)
+        ws = self.ws[self.act_ws]
+        gi = self._gi(self._x(obs, v, None, R, ws), R, ws)
+        hxs = hxs.to(self.device, torch.float32).reshape(N, self.H).contiguous()
+        m = masks.to(self.device, torch.float32).reshape(R).contiguous()
+        hout = torch.empty(R, self.H, device=self.device)
+        H, s = self.H, stream()
+        cnt = ws.get("gru_cnt", call("ppo_gru_seq_counters", N), torch.int32, self.device)
+        call("ppo_gru_seq_fwd_ws", hxs.data_ptr(), m.data_ptr(), None, self.pv(self.GHH), self.pv(self.GBH),
+             gi.data_ptr(), T, N, H, hout.data_ptr(), None, None, None, None, None, cnt.data_ptr(), self.status_ptr(2),
+             s)
+        if int(self.status[2].item()):   # stream-ordered read of the launch's error word
+            self.status[2].zero_()
+            raise RuntimeError("evaluate_actions: the persistent GRU kernel timed out (its outputs are invalid; "
+                               "ppo_gru_persist_set(0) selects the per-step launches)")
+        given = action.to(self.device, torch.float32 if self.float_actions else torch.int64)
+        t = self.towers(hout, R, ws)
+        value, _, logp, ent = self._heads(t["a"][1], R, want_entropy=True, given=given, hv=t["c"][1])
+        return value, logp, ent, hout[(T - 1) * N:]
+
+    @_with_precision
+    def train_minibatch_rec(self, storage, adv, envs, hp, loss_acc, optimizer):
+        """recurrent_generator minibatch (storage.py:162-223): whole T-sequences of
+        the n envs `envs` (int64 device), BPTT over the full T, then one Adam step."""
+        H = self.H
+        if storage.recurrent_hidden_states.shape[-1] != H:
+            raise RuntimeError(f"storage holds hidden states of width {storage.recurrent_hidden_states.shape[-1]}, "
+                               f"the policy's GRU {H}")
+        if storage.obs.dtype != torch.float32 or storage.obs[0, 0].numel() != self.obs_dim:
+            raise RuntimeError(f"MLPBase expects float32 [{self.obs_dim}] observation rows in the storage, got "
+                               f"{storage.obs.dtype} {tuple(storage.obs.shape[2:])}")
+        self.ensure_bound()
+        self.pack()
+        _dist.begin_minibatch()
+        dev, s = self.device, stream()
+        T, N, n = storage.num_steps, storage.rewards.shape[1], envs.numel()
+        R = T * n
+        ws = self.ws["train"]
+        idx = ws.get("ridx", R, torch.int64, dev)[:R]
+        call("ppo_rec_indices", envs.data_ptr(), n, T, N, idx.data_ptr(), s)
+        h0 = ws.get("h0", n * H, device=dev)
+        call("ppo_gather_rows", storage.recurrent_hidden_states.data_ptr(), envs.data_ptr(), h0.data_ptr(), n,
+             4 * H, s)
+        x = self._x(storage.obs, storage.vector_obs if self.V else None, idx, R, ws)
+        gi = self._gi(x, R, ws)
+        hout = ws.get("hout", R * H, device=dev)
+        sv = {k: ws.get("s_" + k, R * H, device=dev) for k in ("r", "z", "n", "ghn", "hin")}
+        masks = storage.masks
+        cnt = ws.get("gru_cnt", call("ppo_gru_seq_counters", n), torch.int32, dev)
+        # error word status[0]: sticky for the update, gates every clip + Adam after a timeout;
+        # no gradient bucket may still be reducing on a side stream beside the persistent launch
+        _dist.assert_no_pending("train_minibatch_rec")
+        call("ppo_gru_seq_fwd_ws", h0.data_ptr(), masks.data_ptr(), idx.data_ptr(), self.pv(self.GHH),
+             self.pv(self.GBH), gi.data_ptr(), T, n, H, hout.data_ptr(), sv["r"].data_ptr(), sv["z"].data_ptr(),
+             sv["n"].data_ptr(), sv["ghn"].data_ptr(), sv["hin"].data_ptr(), cnt.data_ptr(), self.status_ptr(0), s)
+        t = self.towers(hout, R, ws)
+        da2 = ws.get("da2", R * H, device=dev)
+        dc2 = ws.get("dc2", R * H, device=dev)
+        self._heads_train(storage, adv, idx, t["a"][1], R, hp, loss_acc, da2, feat_act=2, feat_v=t["c"][1],
+                          dfeat_v=dc2)
+        d1a, d1c = self._towers_backward(t, hout, R, da2, dc2, H, 0, 0)
+        # dL/d(GRU output): both towers' first layers in one launch, the actor's k range first
+        dout = ws.get("dout", R * H, device=dev)
+        call("ppo_linear_dgrad_pair", d1a.data_ptr(), self.aw1T, H, d1c.data_ptr(), self.cw1T, H, R, H,
+             dout.data_ptr(), s)
+        # backward through time
+        dgi = ws.get("dgi", R * 3 * H, device=dev)
+        dgh = ws.get("dgh", R * 3 * H, device=dev)
+        dhz = ws.get("dhz", n * H, device=dev)
+        carry = ws.get("carry", n * H, device=dev)
+        # persistent BPTT on the same counters (the forward has finished on this stream) and error word
+        _dist.assert_no_pending("train_minibatch_rec bptt")
+        call("ppo_gru_seq_bwd_ws", dout.data_ptr(), sv["r"].data_ptr(), sv["z"].data_ptr(), sv["n"].data_ptr(),
+             sv["ghn"].data_ptr(), sv["hin"].data_ptr(), masks.data_ptr(), idx.data_ptr(), self.whhT, T, n, H,
+             dgi.data_ptr(), dgh.data_ptr(), dhz.data_ptr(), carry.data_ptr(), cnt.data_ptr(), self.status_ptr(0), s)
+        self._dense_wgrad(dgh, sv["hin"], R, 3 * H, H, 0, 0, self.GHH, self.GBH)
+        self._dense_wgrad(dgi, x, R, 3 * H, self.Ip, 3, self.I, self.GIH, self.GBI)
         self._finish_step(optimizer)

@@ -89,6 +89,7 @@ SIGNATURES = {
                         c_f, c_f, c_f, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "ppo_linear_fwd_ex": [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_p],
     "ppo_linear_dgrad_ex": [c_p, c_int, c_int, c_p, c_int, c_p, c_int, c_int, c_p, c_p],
+    "ppo_linear_dgrad_pair": [c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_p],
     "ppo_transpose": [c_p, c_int, c_int, c_p, c_p],
     "ppo_gru_step_fwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "ppo_gru_cell_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p],

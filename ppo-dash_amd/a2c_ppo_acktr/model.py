@@ -140,11 +140,11 @@ class Policy(nn.Module):
             p = next(self.parameters())
             device = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
         if self._engine is None or self._engine.device != device:
-            from ._engine import CNNEngine, MLPEngine, RecurrentEngine
+            from ._engine import CNNEngine, MLPEngine, RecurrentEngine, RecurrentMLPEngine
             if not next(self.parameters()).is_cuda:
                 self.to(device)
             if isinstance(self.base, MLPBase):
-                self._engine = MLPEngine(self, device)
+                self._engine = (RecurrentMLPEngine if self.base.is_recurrent else MLPEngine)(self, device)
             else:
                 self._engine = (RecurrentEngine if self.base.is_recurrent else CNNEngine)(self, device)
         self._engine.ensure_bound()

@@ -306,6 +306,31 @@ PPO_API int ppo_linear_dgrad_ex(const float* dy, int M, int K, const float* wt, 
   return launch(p, M, N, 1, as_stream(stream), "linear_dgrad_ex", 2.0 * M * N * K);
 }
 
+// dx [M][N] = dy0 [M][K0] · wt0 [N][K0]^T + dy1 [M][K1] · wt1 [N][K1]^T: one launch, one accumulator
+// per element, pair 0's k range before pair 1's (DenseDgradPair) — dL/d(GRU output) from MLPBase's
+// critic and actor towers (model.py:231-232)
+PPO_API int ppo_linear_dgrad_pair(const float* dy0, const float* wt0, int K0, const float* dy1, const float* wt1,
+                                  int K1, int M, int N, float* dx, void* stream) {
+  PPO_REQUIRE(K0 > 0 && K1 > 0 && K0 % 4 == 0 && K1 % 4 == 0,
+              "ppo_linear_dgrad_pair: K0=%d K1=%d must be positive multiples of 4", K0, K1);
+  PPO_REQUIRE(M >= 0 && N > 0, "ppo_linear_dgrad_pair: M=%d N=%d", M, N);
+  const double flops = 2.0 * M * N * ((double)K0 + K1);
+#define PPO_DGP(CFG, LAUNCH, VEC)                                                                  \
+  {                                                                                                \
+    DenseDgradPair<CFG> p;                                                                         \
+    p.dy0 = dy0; p.wt0 = wt0; p.dy1 = dy1; p.wt1 = wt1; p.dx = dx; p.M = M; p.N = N; p.K0 = K0; p.K1 = K1; \
+    p.vec = VEC;                                                                                   \
+    return LAUNCH(p, M, N, 1, as_stream(stream), "linear_dgrad_pair", flops);                      \
+  }
+  if (use_x9()) {
+    const int vec = N % 4 == 0 && ((uintptr_t)dx & 15) == 0;
+    if (N <= 64) PPO_DGP(X64, launch_x9, vec)   // the H <= 64 towers: no half-empty 128-column tile
+    PPO_DGP(X128, launch_x9, vec)
+  }
+  PPO_DGP(CfgN128, launch, 0)
+#undef PPO_DGP
+}
+
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ src, int rows, int cols,
                                                         float* __restrict__ dst) {
   const long long total = (long long)rows * cols;

@@ -409,6 +409,38 @@ struct DenseDgradMask : C_ {
   }
 };
 
+// Two-operand data gradient: dx[m][n] = Σ_{k<K0} dy0[m][k] wt0[n][k] + Σ_{k<K1} dy1[m][k] wt1[n][k]
+// — the gradient two layers send into the input they share (MLPBase's actor and critic
+// towers on the GRU output).  One k range of K0 + K1: a 4-wide k group lies in one
+// operand (K0 % 4 == 0, checked by the launcher) and takes its pointer there, so the
+// pair-0 terms run first, then pair 1's, into the one accumulator of each output
+// element; a k tile may straddle K0.  No activation factor.
+template <class C_>
+struct DenseDgradPair : C_ {
+  const float* dy0; const float* wt0; const float* dy1; const float* wt1; float* dx; int M, N, K0, K1;
+  struct ACtx { const float* p0; const float* p1; bool ok; };
+  struct BCtx { const float* p0; const float* p1; bool ok; };
+  __device__ f32x4 load(const float* p0, const float* p1, bool ok, int k) const {
+    if (!ok || k >= K0 + K1) return zero4();
+    return *reinterpret_cast<const f32x4*>(k < K0 ? p0 + k : p1 + (k - K0));
+  }
+  __device__ ACtx a_ctx(int m, int) const { return {dy0 + (size_t)m * K0, dy1 + (size_t)m * K1, m < M}; }
+  __device__ f32x4 a_load(const ACtx& c, int k) const { return load(c.p0, c.p1, c.ok, k); }
+  __device__ BCtx b_ctx(int n, int) const { return {wt0 + (size_t)n * K0, wt1 + (size_t)n * K1, n < N}; }
+  __device__ f32x4 b_load(const BCtx& c, int k) const { return load(c.p0, c.p1, c.ok, k); }
+  __device__ void k_range(int, int& b, int& e) const { b = 0; e = K0 + K1; }
+  __device__ void store(int m, int n, int, float v) const {
+    if (m < M && n < N) dx[(size_t)m * N + n] = v;
+  }
+  // vector epilogue (see DenseDgradMask::store4); vec = 1 only with N % 4 == 0 and dx 16-B aligned
+  static constexpr bool VEC_STORE = true;
+  int vec = 0;
+  __device__ void store4(int m, int n, int, const f32x4& v) const {
+    if (m >= M || n >= N) return;
+    *reinterpret_cast<f32x4*>(dx + (size_t)m * N + n) = v;
+  }
+};
+
 // A operand (row m, k) by branch-free buffer loads (see DenseWgradB): byte offset
 // m·ld·4 + k·4 in one resource over rows [0, M); a row past M starts out of range
 // (0x80000000) and k ≥ K is sent there by a select, so each load is one v_cndmask
