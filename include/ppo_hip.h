@@ -263,7 +263,8 @@ int ppo_colsum(const float* src, long long ld, int rows, long long cols, float* 
  *   "stagger"     schedule bits 0..15 (default 2; every value gives the same results);
  *                 larger values are refused (they select timing-anatomy paths that give
  *                 wrong results by design, accepted only by a -DPPO_DIAG build)
- *   "small_b"     forwards of at most this many samples take small.hip's kernels (>= 0)
+ *   "small_b"     forwards of at most this many samples take small.hip's kernels (>= 0;
+ *                 conv1 with more than 8 channels keeps its tile GEMM)
  *   "heads_lds"   0 / non-zero: the LDS-weight heads_train kernel off / on (default on) */
 int ppo_tune_set(const char* key, int value);
 /* current value of a tune key (-1 if unknown) */

@@ -416,7 +416,9 @@ using CfgW32 = Cfg<32, 256, 1, 4, false, false, true>;
 static int conv1_fwd_impl(const void* obs, int obs_is_u8, const int64_t* idx, long long row0, int C, int B,
                           const float* w1, const float* b1, float* out, uint16_t* mbits, void* stream) {
   PPO_REQUIRE(B >= 0 && C > 0, "ppo_conv1_fwd: B=%d C=%d", B, C);
-  if (!mbits && B > 0 && B <= tune_small_b())
+  // small.hip's kernel combines at most 8 channel partials per output: more channels (four
+  // stacked RGB frames: C = 12) take the tile GEMM below at every batch size
+  if (!mbits && B > 0 && B <= tune_small_b() && C <= 8)
     return small_conv1_fwd(obs, obs_is_u8, idx, row0, C, B, w1, b1, out, as_stream(stream));
   // float observations (the reference's fp32 storage plane): the image-resident
   // split-bf16 kernel of conv1f.hip
@@ -486,6 +488,7 @@ PPO_API int ppo_conv1_wgrad(const float* dz1, const void* obs, int obs_is_u8, co
                             int C, int B, int Z, float* slab, float* slab_bias, void* stream) {
   const long long R = (long long)B * 400;
   PPO_REQUIRE(R < 0x7fffffffLL, "ppo_conv1_wgrad: B too large");
+  if (B <= 0 || Z <= 0) return 0;   // every path: an empty launch writes nothing (the tile GEMM wrote zero slabs)
   const double fl = 2.0 * R * 32 * C * 64;
   // u8 rows, C = 4: the k-split kernels (conv1w.hip, tunes 8-10, fp32 dz) or the
   // part-pipelined kernel (tune 5; the half-precision mode's, bf16 dz)
