@@ -448,6 +448,32 @@ int ppo_heads_bern_train(const float* feat, const float* feat_v, int B, int H, c
                          const float* ret, float clip, float value_coef, float entropy_coef, float inv_b,
                          int use_clipped_value_loss, int feat_act, float* dfeat, float* dfeat_v, float* part_w,
                          float* part_b, float* part_loss, void* stream);
+/* The three act entry points with the sampling counter as a word in device memory
+ * instead of a launch argument: `counter` is a device pointer to one 8-byte word.
+ * Each kernel reads it once per wave, uses the value exactly where its by-value
+ * sibling uses `counter` (same results bit for bit for the same value) and never
+ * writes it.  A launch argument freezes when the launch is captured into a HIP
+ * graph; the word does not, so a captured act samples anew at every replay when a
+ * captured ppo_rng_advance follows it.  The word must be a valid pointer even when
+ * it is not used (noise / given / deterministic); NULL is refused with PPO_EARG
+ * before any HIP call.  Every other argument is the by-value function's. */
+int ppo_heads_act_dc(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                     const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+                     const unsigned long long* counter, int deterministic, const int64_t* given, float* value,
+                     int64_t* action, float* logp, float* entropy, void* stream);
+int ppo_heads_gauss_act_dc(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                           const float* wa, const float* ba, const float* logstd, int A, const float* noise,
+                           unsigned long long seed, const unsigned long long* counter, int deterministic,
+                           const float* given, float* value, float* action, float* logp, float* entropy,
+                           void* stream);
+int ppo_heads_bern_act_dc(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                          const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+                          const unsigned long long* counter, int deterministic, const float* given, float* value,
+                          float* action, float* logp, float* entropy, void* stream);
+/* *counter += by (64-bit wrap-around), one thread, a launch of its own on `stream`:
+ * after the act kernel that read the word, because an increment inside that kernel
+ * would race with the blocks that have not read it yet.  NULL: PPO_EARG. */
+int ppo_rng_advance(unsigned long long* counter, unsigned long long by, void* stream);
 /* model.py:77 dist.entropy().mean() */
 int ppo_mean_f32(const float* x, long long n, float* out, void* stream);
 

@@ -114,6 +114,32 @@ class CNNEngine:
         # (sticky; gates clip + Adam), [1] optimizer steps skipped by a guard,
         # [2] persistent-GRU timeout of evaluate_sequence
         self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self._rng_dev = None      # the sampling counter as a device word (rng_dev), allocated at first use
+        self._device_counter = False
+
+    @property
+    def rng_dev(self):
+        """The sampling counter as one 8-byte word in device memory: what the kernels of a
+        captured HIP graph read (a launch argument would freeze in the graph)."""
+        if self._rng_dev is None:
+            self._rng_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._rng_dev
+
+    def set_rng_dev(self, value):
+        """rng_dev = value mod 2^64, as a stream-ordered fill"""
+        v = int(value) & 0xFFFFFFFFFFFFFFFF
+        self.rng_dev.fill_(v - (1 << 64) if v >> 63 else v)   # the int64 tensor holds the same 64 bits
+
+    @contextlib.contextmanager
+    def using_device_counter(self):
+        """Inside, the heads read the sampling counter from rng_dev (the _dc entry points)
+        and a launch of its own advances the word by one after them; the host rng_counter
+        is left alone.  The caller keeps the two in step (evaluation.GraphedActor)."""
+        prev, self._device_counter = self._device_counter, True
+        try:
+            yield self.rng_dev
+        finally:
+            self._device_counter = prev
 
     def status_ptr(self, i):
         return self.status.data_ptr() + 4 * i
@@ -314,30 +340,36 @@ class CNNEngine:
             noise = noise.to(self.device, torch.float32).contiguous()
             if noise.shape != (B, self.A):
                 raise RuntimeError(f"noise must be [{B},{self.A}]")
-        self.rng_counter += 1
+        if self._device_counter:   # using_device_counter(): the word, advanced by a launch after the heads
+            counter, dc = self.rng_dev.data_ptr(), "_dc"
+        else:
+            self.rng_counter += 1
+            counter, dc = self.rng_counter, ""
         if self.float_actions and given is not None and given.numel() != B * self.A:
             raise RuntimeError(f"actions must be [{B},{self.A}], got {tuple(given.shape)}")
         if self.dist_kind == "bern":
-            call("ppo_heads_bern_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
-                 self.pv(self.WA), self.pv(self.BA), self.A, ptr(noise), self.rng_seed, self.rng_counter,
+            call("ppo_heads_bern_act" + dc, h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), self.A, ptr(noise), self.rng_seed, counter,
                  int(bool(deterministic)),
                  ptr(given.reshape(-1).contiguous() if given is not None else None, torch.float32, "action"),
                  value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
                  ptr(logp), ptr(ent), stream())
-            return value, action, logp, ent
-        if self.gauss:
-            call("ppo_heads_gauss_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
+        elif self.gauss:
+            call("ppo_heads_gauss_act" + dc, h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
                  self.pv(self.WA), self.pv(self.BA), self.pv(self.LS), self.A, ptr(noise), self.rng_seed,
-                 self.rng_counter, int(bool(deterministic)),
+                 counter, int(bool(deterministic)),
                  ptr(given.reshape(-1).contiguous() if given is not None else None, torch.float32, "action"),
                  value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
                  ptr(logp), ptr(ent), stream())
-            return value, action, logp, ent
-        call("ppo_heads_act", h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC), self.pv(self.WA),
-             self.pv(self.BA), self.A, ptr(noise), self.rng_seed, self.rng_counter, int(bool(deterministic)),
-             ptr(given.reshape(-1).contiguous() if given is not None else None, torch.int64, "action"),
-             value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
-             ptr(logp), ptr(ent), stream())
+        else:
+            call("ppo_heads_act" + dc, h.data_ptr(), ptr(hv), B, self.H, self.pv(self.WC), self.pv(self.BC),
+                 self.pv(self.WA), self.pv(self.BA), self.A, ptr(noise), self.rng_seed, counter,
+                 int(bool(deterministic)),
+                 ptr(given.reshape(-1).contiguous() if given is not None else None, torch.int64, "action"),
+                 value.data_ptr(), None if given is not None or value_only else action.data_ptr(),
+                 ptr(logp), ptr(ent), stream())
+        if self._device_counter:
+            call("ppo_rng_advance", self.rng_dev.data_ptr(), 1, stream())
         return value, action, logp, ent
 
     def mean(self, x):

@@ -124,6 +124,15 @@ SIGNATURES = {
                            c_p, c_p, c_p],
     "ppo_heads_bern_train": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_p, c_p, c_p,
                              c_f, c_f, c_f, c_f, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
+    # the act entry points with the sampling counter as a device word (c_p where the by-value
+    # functions take c_ull), and the launch that advances the word
+    "ppo_heads_act_dc": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ull, c_p, c_int, c_p, c_p, c_p,
+                         c_p, c_p, c_p],
+    "ppo_heads_gauss_act_dc": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_ull, c_p, c_int, c_p,
+                               c_p, c_p, c_p, c_p, c_p],
+    "ppo_heads_bern_act_dc": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ull, c_p, c_int, c_p, c_p,
+                              c_p, c_p, c_p, c_p],
+    "ppo_rng_advance": [c_p, c_ull, c_p],
     # obs.hip
     "ppo_obs_preprocess": [c_p, c_ll, c_int, c_int, c_int, c_p, c_d, c_int, c_p, c_ll, c_p],
     "ppo_frame_stack": [c_p, c_int, c_int, c_ll, c_p, c_p, c_int, c_p],

@@ -71,12 +71,14 @@ __global__ __launch_bounds__(64 * HW) void heads_act_kernel(
     const float* __restrict__ feat, const float* __restrict__ feat_v_, int N, int H_, const float* __restrict__ wc,
     const float* __restrict__ bc, const float* __restrict__ wa, const float* __restrict__ ba, int A_,
     const float* __restrict__ noise,
-    unsigned long long seed, unsigned long long counter, int deterministic, const int64_t* __restrict__ given,
+    unsigned long long seed, unsigned long long counter_v, const unsigned long long* __restrict__ counter_p,
+    int deterministic, const int64_t* __restrict__ given,
     float* __restrict__ value_out, int64_t* __restrict__ action_out, float* __restrict__ logp_out,
     float* __restrict__ ent_out, int rows_per_wave) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int H = FAST ? 64 * HC : H_, A = FAST ? AMAX : A_;
   const float* const feat_v = FAST ? nullptr : feat_v_;
+  const uint64_t counter = rng_counter_of(counter_p, counter_v);
   HeadW<HC, AMAX> w;
   load_head_w(w, wc, wa, A, H, lane);
   const float b0 = bc[0];
@@ -506,41 +508,66 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ x, 
   if (threadIdx.x == 0) out[0] = (float)(r[0] / (double)n);
 }
 
+// the arguments of one act launch (counter_p: the sampling counter as a word in device
+// memory, read by the kernel; NULL: the by-value counter)
+struct ActCall {
+  const float *feat, *feat_v;
+  int N, H;
+  const float *wc, *bc, *wa, *ba;
+  int A;
+  const float* noise;
+  unsigned long long seed, counter;
+  const unsigned long long* counter_p;
+  int det;
+  const int64_t* given;
+  float* v;
+  int64_t* act;
+  float *lp, *ent;
+};
+
 template <int HC, int AMAX>
-int launch_act(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc, const float* wa,
-               const float* ba,
-               int A, const float* noise, unsigned long long seed, unsigned long long counter, int det,
-               const int64_t* given, float* v, int64_t* act, float* lp, float* ent, hipStream_t st) {
+int launch_act(const ActCall& c, hipStream_t st) {
   // ~4096 waves in flight (4 per SIMD at this kernel's 122-137 VGPRs): a rollout batch of
   // 4,096 rows takes one row per wave, so no wave runs two rows' dependent chains back to back
-  const int rpw = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(N, 4096)));
-  const unsigned blocks = ceil_div(N, HW * rpw);
-  if (A == AMAX && H == 64 * HC && !feat_v)
-    heads_act_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter,
-                                                        det,
-                                                        given, v, act, lp, ent, rpw);
+  const int rpw = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(c.N, 4096)));
+  const unsigned blocks = ceil_div(c.N, HW * rpw);
+  if (c.A == AMAX && c.H == 64 * HC && !c.feat_v)
+    heads_act_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(c.feat, c.feat_v, c.N, c.H, c.wc, c.bc, c.wa, c.ba, c.A,
+                                                        c.noise, c.seed, c.counter, c.counter_p, c.det, c.given, c.v,
+                                                        c.act, c.lp, c.ent, rpw);
   else
-    heads_act_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter,
-                                                        det,
-                                                        given, v, act, lp, ent, rpw);
+    heads_act_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(c.feat, c.feat_v, c.N, c.H, c.wc, c.bc, c.wa, c.ba, c.A,
+                                                         c.noise, c.seed, c.counter, c.counter_p, c.det, c.given, c.v,
+                                                         c.act, c.lp, c.ent, rpw);
   PPO_LAUNCH_CHECK("heads_act_kernel");
   return 0;
 }
 
 template <int AMAX>
-int dispatch_act(int HC, const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
-                 const float* wa,
-                 const float* ba, int A, const float* noise, unsigned long long seed, unsigned long long counter,
-                 int det, const int64_t* given, float* v, int64_t* act, float* lp, float* ent, hipStream_t st) {
+int dispatch_act(int HC, const ActCall& c, hipStream_t st) {
   switch (HC) {
-    case 1: return launch_act<1, AMAX>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, det, given, v, act, lp, ent, st);
-    case 2: return launch_act<2, AMAX>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, det, given, v, act, lp, ent, st);
-    case 4: return launch_act<4, AMAX>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, det, given, v, act, lp, ent, st);
-    case 8: return launch_act<8, AMAX>(feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, det, given, v, act, lp, ent, st);
+    case 1: return launch_act<1, AMAX>(c, st);
+    case 2: return launch_act<2, AMAX>(c, st);
+    case 4: return launch_act<4, AMAX>(c, st);
+    case 8: return launch_act<8, AMAX>(c, st);
   }
-  ppo_set_error("heads: hidden size %d not supported (<= 512)", H);
+  ppo_set_error("heads: hidden size %d not supported (<= 512)", c.H);
   return PPO_EARG;
 }
+
+// ppo_heads_act / ppo_heads_act_dc after their argument checks
+int heads_act(const char* name, const ActCall& c, void* stream) {
+  PPO_REQUIRE(c.N >= 0 && c.A >= 1 && c.A <= 16, "%s: N=%d A=%d (1..16 actions)", name, c.N, c.A);
+  PPO_REQUIRE(c.H > 0 && c.H <= 512, "%s: hidden size %d (1..512)", name, c.H);
+  ProfScope prof("heads_act", as_stream(stream), (double)c.N * (4.0 * c.H * (c.feat_v ? 2 : 1) + 16.0));
+  if (c.N == 0) return 0;
+  if (c.A <= 8) return dispatch_act<8>(hc_of(c.H), c, as_stream(stream));
+  return dispatch_act<16>(hc_of(c.H), c, as_stream(stream));
+}
+
+// *counter += by, after the act kernel that read it (stream order): an increment inside
+// that kernel would race with the blocks that have not read the word yet
+__global__ void rng_advance_kernel(unsigned long long* counter, unsigned long long by) { *counter += by; }
 
 template <int HC, int AMAX>
 int launch_train(const TrainArgs& a, int blocks, hipStream_t st) {
@@ -583,17 +610,30 @@ PPO_API int ppo_heads_act(const float* feat, const float* feat_v, int N, int H, 
                           const float* ba, int A, const float* noise, unsigned long long seed,
                           unsigned long long counter, int deterministic, const int64_t* given, float* value,
                           int64_t* action, float* logp, float* entropy, void* stream) {
-  PPO_REQUIRE(N >= 0 && A >= 1 && A <= 16, "ppo_heads_act: N=%d A=%d (1..16 actions)", N, A);
-  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_act: hidden size %d (1..512)", H);
-  ProfScope prof("heads_act", as_stream(stream), (double)N * (4.0 * H * (feat_v ? 2 : 1) + 16.0));
-  if (N == 0) return 0;
-  hipStream_t st = as_stream(stream);
-  const int HC = hc_of(H);
-  if (A <= 8)
-    return dispatch_act<8>(HC, feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, deterministic, given, value,
-                           action, logp, entropy, st);
-  return dispatch_act<16>(HC, feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, deterministic, given, value,
-                          action, logp, entropy, st);
+  const ActCall c = {feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, nullptr, deterministic, given,
+                     value, action, logp, entropy};
+  return heads_act("ppo_heads_act", c, stream);
+}
+
+// ppo_heads_act with the counter in device memory: one 8-byte word that the kernel reads
+// (once per wave) and never writes, so a launch captured into a HIP graph samples anew at
+// every replay once ppo_rng_advance follows it on the stream
+PPO_API int ppo_heads_act_dc(const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+                             const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+                             const unsigned long long* counter, int deterministic, const int64_t* given,
+                             float* value, int64_t* action, float* logp, float* entropy, void* stream) {
+  PPO_REQUIRE(counter != nullptr, "ppo_heads_act_dc: counter is NULL (a device pointer to one 8-byte word)");
+  const ActCall c = {feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, 0ull, counter, deterministic, given,
+                     value, action, logp, entropy};
+  return heads_act("ppo_heads_act_dc", c, stream);
+}
+
+// *counter += by (64-bit wrap-around) as a launch of its own on `stream`
+PPO_API int ppo_rng_advance(unsigned long long* counter, unsigned long long by, void* stream) {
+  PPO_REQUIRE(counter != nullptr, "ppo_rng_advance: counter is NULL (a device pointer to one 8-byte word)");
+  rng_advance_kernel<<<1, 1, 0, as_stream(stream)>>>(counter, by);
+  PPO_LAUNCH_CHECK("rng_advance_kernel");
+  return 0;
 }
 
 PPO_API int ppo_heads_train_blocks(int B) {

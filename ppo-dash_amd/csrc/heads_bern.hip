@@ -61,6 +61,7 @@ struct ActArgs {
   const float *wc, *bc, *wa, *ba;
   const float* noise;      // [N][A] uniform draws in [0, 1) (host replay) or NULL
   unsigned long long seed, counter;
+  const unsigned long long* counter_p;   // the counter as a word in device memory, or NULL (by value)
   int deterministic;
   const float* given;      // [N][A] actions to evaluate or NULL
   float *value, *action, *logp, *entropy;
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(64 * HW) void bern_act_kernel(const ActArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int H = FAST ? 64 * HC : a.H, A = FAST ? AMAX : a.A;
   const float* const feat_v = FAST ? nullptr : a.feat_v;
+  const uint64_t counter = rng_counter_of(a.counter_p, a.counter);
   HeadW<HC, AMAX> w;
   load_head_w(w, a.wc, a.wa, A, H, lane);
   const float b0 = a.bc[0];
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(64 * HW) void bern_act_kernel(const ActArgs a) {
         } else if (a.deterministic) {
           act[o] = t.p > 0.5f ? 1.f : 0.f;   // torch.gt(probs, 0.5): p == 0.5 gives 0
         } else {
-          const float u = a.noise ? a.noise[row * A + o] : uniform_noise(a.seed, a.counter, row, o, A);
+          const float u = a.noise ? a.noise[row * A + o] : uniform_noise(a.seed, counter, row, o, A);
           act[o] = u < t.p ? 1.f : 0.f;
         }
         lp += act[o] * z[o] - fmaxf(z[o], 0.f) - t.sp;
@@ -525,6 +527,19 @@ int dispatch_train(int HC, const BernTrainArgs& a, int blocks, hipStream_t st) {
   return PPO_EARG;
 }
 
+// ppo_heads_bern_act / ppo_heads_bern_act_dc after the latter's counter check
+int bern_act(const char* name, ActArgs a, void* stream) {
+  PPO_REQUIRE(a.N >= 0 && a.A >= 1 && a.A <= 16, "%s: N=%d A=%d (1..16 action dimensions)", name, a.N, a.A);
+  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
+  ProfScope prof("heads_bern_act", as_stream(stream),
+                 (double)a.N * (4.0 * a.H * (a.feat_v ? 2 : 1) + 12.0 + 4.0 * a.A));
+  if (a.N == 0) return 0;
+  // as ppo_heads_act: ~4096 waves in flight, one row per wave at a rollout batch of 4,096
+  a.rows_per_wave = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(a.N, 4096)));
+  if (a.A <= 8) return dispatch_act<8>(hc_of(a.H), a, as_stream(stream));
+  return dispatch_act<16>(hc_of(a.H), a, as_stream(stream));
+}
+
 }  // namespace
 
 // Policy.act / get_value / evaluate_actions heads for FixedBernoulli(logits):
@@ -536,18 +551,26 @@ PPO_API int ppo_heads_bern_act(const float* feat, const float* feat_v, int N, in
                                const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
                                unsigned long long counter, int deterministic, const float* given, float* value,
                                float* action, float* logp, float* entropy, void* stream) {
-  PPO_REQUIRE(N >= 0 && A >= 1 && A <= 16, "ppo_heads_bern_act: N=%d A=%d (1..16 action dimensions)", N, A);
-  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_bern_act: hidden size %d (1..512)", H);
-  ProfScope prof("heads_bern_act", as_stream(stream), (double)N * (4.0 * H * (feat_v ? 2 : 1) + 12.0 + 4.0 * A));
-  if (N == 0) return 0;
   ActArgs a;
   a.feat = feat; a.feat_v = feat_v; a.N = N; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.noise = noise; a.seed = seed; a.counter = counter; a.deterministic = deterministic;
+  a.noise = noise; a.seed = seed; a.counter = counter; a.counter_p = nullptr; a.deterministic = deterministic;
   a.given = given; a.value = value; a.action = action; a.logp = logp; a.entropy = entropy;
-  // as ppo_heads_act: ~4096 waves in flight, one row per wave at a rollout batch of 4,096
-  a.rows_per_wave = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(N, 4096)));
-  if (A <= 8) return dispatch_act<8>(hc_of(H), a, as_stream(stream));
-  return dispatch_act<16>(hc_of(H), a, as_stream(stream));
+  return bern_act("ppo_heads_bern_act", a, stream);
+}
+
+// ppo_heads_bern_act with the counter in device memory (see ppo_heads_act_dc): one 8-byte
+// word, read once per wave and never written
+PPO_API int ppo_heads_bern_act_dc(const float* feat, const float* feat_v, int N, int H, const float* wc,
+                                  const float* bc, const float* wa, const float* ba, int A, const float* noise,
+                                  unsigned long long seed, const unsigned long long* counter, int deterministic,
+                                  const float* given, float* value, float* action, float* logp, float* entropy,
+                                  void* stream) {
+  PPO_REQUIRE(counter != nullptr, "ppo_heads_bern_act_dc: counter is NULL (a device pointer to one 8-byte word)");
+  ActArgs a;
+  a.feat = feat; a.feat_v = feat_v; a.N = N; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
+  a.noise = noise; a.seed = seed; a.counter = 0; a.counter_p = counter; a.deterministic = deterministic;
+  a.given = given; a.value = value; a.action = action; a.logp = logp; a.entropy = entropy;
+  return bern_act("ppo_heads_bern_act_dc", a, stream);
 }
 
 // the Bernoulli ppo_heads_train: same launch shape (ppo_heads_train_blocks) and the

@@ -1,6 +1,7 @@
 // Pieces shared by the Categorical (heads.hip) and DiagGaussian (heads_gauss.hip)
 // head kernels: the per-lane head-weight registers, the 1 + A wave-reduced dot
-// products, the activation gradient and the loss-partial reduction.
+// products, the sampling counter's source, the activation gradient and the
+// loss-partial reduction.
 #pragma once
 #include "common.h"
 
@@ -45,6 +46,15 @@ __device__ __forceinline__ void head_dots(const HeadW<HC, AMAX>& w, const float 
       z[o] = -INFINITY;
     }
   }
+}
+
+// The sampling counter of an act launch: the by-value argument, or, for the _dc entry
+// points, the word in device memory that `p` names.  `p` is a kernel argument, so the
+// read is one uniform load per wave; the kernels never write the word (ppo_rng_advance
+// does, in a launch of its own).
+__device__ __forceinline__ uint64_t rng_counter_of(const unsigned long long* __restrict__ p,
+                                                   unsigned long long by_value) {
+  return p ? *p : by_value;
 }
 
 // d(pre-activation) from d(output) for the activation that produced y
