@@ -63,11 +63,10 @@ class GraphedActor(object):
         self.policy, self.device, self.warmup = policy, eng.device, warmup
         self.carry_hidden = bool(carry_hidden) and policy.is_recurrent
         self.sample = bool(sample)
-        self.mlp = hasattr(eng, "obs_dim")   # MLPEngine / RecurrentMLPEngine: 1-D observations
         V = getattr(eng, "V", getattr(policy.base, "vector_obs_len", 0))
         Hh = policy.recurrent_hidden_state_size   # eng.H for a recurrent base, else 1
         dev = self.device
-        if self.mlp:
+        if eng.is_mlp:   # MLPEngine / RecurrentMLPEngine: 1-D observations
             self.obs = torch.zeros(num_envs, eng.obs_dim, device=dev)
         else:
             self.obs = torch.zeros(num_envs, eng.C, 84, 84, dtype=obs_dtype, device=dev)
@@ -97,7 +96,7 @@ class GraphedActor(object):
                 self.out = self._act()
                 if self.carry_hidden:   # h' -> the next replay's h, inside the graph
                     self.hxs.copy_(self.out[3])
-        self._key = self._pack_key()
+        self._key = self.eng.pack_key()
         self._ptrs = self._pointers()
         self.captures += 1
         if self.sample:   # the warm-up acts advanced the word; the host counter did not move
@@ -107,20 +106,13 @@ class GraphedActor(object):
         with torch.no_grad():
             if not self.sample:
                 return self.policy.act(self.obs, self.vec, self.hxs, self.masks, deterministic=True)
-            # Policy.act's dispatch (model.py:54-66) with the counter read from the device word
-            # and, in 'host' mode, the noise from ga.noise
-            eng = self.eng
-            noise = self.noise if self._mode == "host" else None
-            with eng.using_device_counter():
-                if self.policy.is_recurrent:
-                    value, action, logp, _, hxs = eng.act(self.obs, deterministic=False, noise=noise, vec=self.vec,
-                                                          hxs=self.hxs, masks=self.masks)
-                    return value, action, logp, hxs
-                if self.mlp:
-                    value, action, logp, _ = eng.act(self.obs, deterministic=False, noise=noise, vec=self.vec)
-                else:
-                    value, action, logp, _ = eng.act(self.obs, deterministic=False, noise=noise)
-                return value, action, logp, self.hxs
+            # Policy.act (model.py:54-66) with the counter read from the device word and, in
+            # 'host' mode, the noise from ga.noise
+            with self.eng.using_device_counter():
+                value, action, logp, _, hxs = _model.engine_act(
+                    self.eng, self.obs, self.vec, self.hxs, self.masks, deterministic=False,
+                    noise=self.noise if self._mode == "host" else None)
+            return value, action, logp, hxs
 
     def _sync_counter(self, force=False):
         """the device word = the counter the next act uses (rng_counter + 1), rewritten when
@@ -135,9 +127,6 @@ class GraphedActor(object):
             self.eng.rng_counter += 1
             self._synced += 1
         return self.out
-
-    def _pack_key(self):
-        return (sum(p._version for p in self.eng.params), self.eng.epoch)
 
     def _pointers(self):
         """every buffer address baked into the graph that could be reallocated, and
@@ -159,9 +148,9 @@ class GraphedActor(object):
         eng = self.policy.hip_engine(self.device)
         if eng is not self.eng or self._pointers() != self._ptrs:
             self._capture()
-        elif self._pack_key() != self._key:
+        elif self.eng.pack_key() != self._key:
             self.eng.pack(force=True)
-            self._key = self._pack_key()
+            self._key = self.eng.pack_key()
         if self.sample:
             self._sync_counter()
 

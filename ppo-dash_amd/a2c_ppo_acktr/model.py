@@ -166,46 +166,32 @@ class Policy(nn.Module):
         """model.py:54-66 -> (value [N,1], action [N,1] int64 (Box: [N,A] float; MultiBinary: [N,A] float
         holding 0.0 / 1.0), action_log_probs [N,1], rnn_hxs)."""
         eng = self.hip_engine()
-        n = visual_inputs.shape[0]
-        noise = None if deterministic else self._noise(n)
-        if self.is_recurrent:
-            value, action, logp, _, rnn_hxs = eng.act(visual_inputs, deterministic=deterministic, noise=noise,
-                                                      vec=vector_inputs, hxs=rnn_hxs, masks=masks)
-            return value, action, logp, rnn_hxs
-        if isinstance(self.base, MLPBase):
-            value, action, logp, _ = eng.act(visual_inputs, deterministic=deterministic, noise=noise,
-                                             vec=vector_inputs)
-            return value, action, logp, rnn_hxs
-        value, action, logp, _ = eng.act(visual_inputs, deterministic=deterministic, noise=noise)
+        noise = None if deterministic else self._noise(visual_inputs.shape[0])
+        value, action, logp, _, rnn_hxs = engine_act(eng, visual_inputs, vector_inputs, rnn_hxs, masks,
+                                                     deterministic=deterministic, noise=noise)
         return value, action, logp, rnn_hxs
 
     def get_value(self, visual_inputs, vector_inputs, rnn_hxs, masks):
         """model.py:68-70."""
-        eng = self.hip_engine()
-        if self.is_recurrent:
-            return eng.act(visual_inputs, value_only=True, vec=vector_inputs, hxs=rnn_hxs, masks=masks)[0]
-        if isinstance(self.base, MLPBase):
-            return eng.act(visual_inputs, value_only=True, vec=vector_inputs)[0]
-        value, _, _, _ = eng.act(visual_inputs, value_only=True)
-        return value
+        return engine_act(self.hip_engine(), visual_inputs, vector_inputs, rnn_hxs, masks, value_only=True)[0]
 
     def evaluate_actions(self, visual_inputs, vector_inputs, rnn_hxs, masks, action):
         """model.py:72-79 -> (value [B,1], action_log_probs [B,1], dist_entropy (0-d), rnn_hxs)."""
         eng = self.hip_engine()
         action = action.to(eng.device, torch.float32 if eng.float_actions else torch.int64)
-        if self.is_recurrent:
-            if visual_inputs.shape[0] == rnn_hxs.shape[0]:   # model.py:112 single-step branch
-                value, _, logp, ent, rnn_hxs = eng.act(visual_inputs, given=action, want_entropy=True,
-                                                       vec=vector_inputs, hxs=rnn_hxs, masks=masks)
-            else:                                             # model.py:116-165 sequence branch
-                value, logp, ent, rnn_hxs = eng.evaluate_sequence(visual_inputs, vector_inputs, rnn_hxs, masks,
-                                                                  action)
-            return value, logp, eng.mean(ent), rnn_hxs
-        if isinstance(self.base, MLPBase):
-            value, _, logp, ent = eng.act(visual_inputs, given=action, want_entropy=True, vec=vector_inputs)
-        else:
-            value, _, logp, ent = eng.act(visual_inputs, given=action, want_entropy=True)
+        if self.is_recurrent and visual_inputs.shape[0] != rnn_hxs.shape[0]:   # model.py:116-165 sequence branch
+            value, logp, ent, rnn_hxs = eng.evaluate_sequence(visual_inputs, vector_inputs, rnn_hxs, masks, action)
+        else:                                                                  # model.py:112 single-step branch
+            value, _, logp, ent, rnn_hxs = engine_act(eng, visual_inputs, vector_inputs, rnn_hxs, masks,
+                                                      given=action, want_entropy=True)
         return value, logp, eng.mean(ent), rnn_hxs
+
+
+def engine_act(eng, obs, vec, hxs, masks, **kw):
+    """eng.act for any of the four engines -> (value, action, logp, entropy, hxs): a feed-forward
+    engine ignores the arguments it has no use for and hands hxs back as it came."""
+    out = eng.act(obs, vec=vec, hxs=hxs, masks=masks, **kw)
+    return out if eng.recurrent else (*out, hxs)
 
 
 class NNBase(nn.Module):

@@ -526,3 +526,25 @@ def test_wrong_hidden_width_storage_raises_before_any_launch(gpu):
     torch.cuda.synchronize()
     assert not eng.ws["train"].bufs and opt.step_count == 0   # no workspace was touched, no step taken
     assert not eng.grad.any() and not loss.any()
+
+
+def test_cnn_wrong_hidden_width_storage_raises_before_any_launch(gpu):
+    """RecurrentEngine shares the prologue of train_minibatch_rec, so the same check guards its
+    ppo_gather_rows (4 H bytes per row of the stored hidden states): nothing is launched."""
+    from a2c_ppo_acktr import model as M
+    from a2c_ppo_acktr.algo.ppo import FlatAdam
+    from a2c_ppo_acktr.storage import RolloutStorage
+    from a2c_ppo_acktr.synthetic import Discrete
+    T, N, C, H, A = 3, 4, 4, 64, 2
+    torch.manual_seed(0)
+    pol = M.Policy((C, 84, 84), Discrete(A), base=M.CNNBase, base_kwargs={"recurrent": True, "hidden_size": H}).to(gpu)
+    eng = pol.hip_engine()
+    assert type(eng).__name__ == "RecurrentEngine"
+    st = RolloutStorage(T, N, (C, 84, 84), [0], Discrete(A), 32, obs_dtype=torch.uint8, device=gpu)
+    loss = torch.zeros(4, dtype=torch.float64, device=gpu)
+    opt = FlatAdam(pol.parameters(), lr=1e-3, eps=1e-5, max_grad_norm=None)
+    with pytest.raises(RuntimeError, match="hidden states of width 32"):
+        eng.train_minibatch_rec(st, torch.zeros(T, N, device=gpu), torch.arange(2, device=gpu), HP, loss, opt)
+    torch.cuda.synchronize()
+    assert not eng.ws["train"].bufs and opt.step_count == 0   # no workspace was touched, no step taken
+    assert not eng.grad.any() and not loss.any()
