@@ -448,6 +448,32 @@ int ppo_heads_bern_train(const float* feat, const float* feat_v, int B, int H, c
                          const float* ret, float clip, float value_coef, float entropy_coef, float inv_b,
                          int use_clipped_value_loss, int feat_act, float* dfeat, float* dfeat_v, float* part_w,
                          float* part_b, float* part_loss, void* stream);
+/* The three train entry points with A2C's row loss (algo/a2c_acktr.py:45-51, 71-72)
+ * in place of PPO's: per row adv = ret - value (fp32, detached), dL/dlog_prob =
+ * -inv_b adv, dL/dvalue = value_coef inv_b 2 (value - ret) (A2C's value loss has no
+ * 0.5); the entropy term and everything downstream are the PPO functions'.  Only the
+ * actions and the returns of the storage are read: old log-probs, advantages and value
+ * predictions are not arguments.  Same argument checks, launch shape
+ * (ppo_heads_train_blocks), kernel selection and partial layouts as the sibling without
+ * the suffix, and the same reduce: part_loss slot 0 holds sum 2 (ret - value)^2, so that
+ * ppo_heads_reduce / ppo_heads_gauss_reduce, which halve slot 0 (0.5 sum / B), leave
+ * mean((ret - value)^2) in loss_acc[0]; slot 1 holds sum adv log_prob (loss_acc[1] +=
+ * -sum / B), slots 2 and 3 the entropy sum and the bad-action count as for PPO. */
+int ppo_heads_train_a2c(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
+                        const float* wa, const float* ba, int A, const int64_t* idx, long long row0,
+                        const int64_t* actions, const float* ret, float value_coef, float entropy_coef, float inv_b,
+                        int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b, float* part_loss,
+                        void* stream);
+int ppo_heads_gauss_train_a2c(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
+                              const float* wa, const float* ba, const float* logstd, int A, const int64_t* idx,
+                              long long row0, const float* actions, const float* ret, float value_coef,
+                              float entropy_coef, float inv_b, int feat_act, float* dfeat, float* dfeat_v,
+                              float* part_w, float* part_b, float* part_loss, void* stream);
+int ppo_heads_bern_train_a2c(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
+                             const float* wa, const float* ba, int A, const int64_t* idx, long long row0,
+                             const float* actions, const float* ret, float value_coef, float entropy_coef,
+                             float inv_b, int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
+                             float* part_loss, void* stream);
 /* The three act entry points with the sampling counter as a word in device memory
  * instead of a launch argument: `counter` is a device pointer to one 8-byte word.
  * Each kernel reads it once per wave, uses the value exactly where its by-value
@@ -492,6 +518,16 @@ int ppo_clip_adam_guarded(float* params, float* grads, float* exp_avg, float* ex
                           const double* partials, float scale, double max_norm, double lr, double beta1,
                           double beta2, double eps, long long step, double* norm_out, const int* guard_i,
                           const double* guard_d, int* skipped, void* stream);
+/* clip_grad_norm_ + optim.RMSprop(lr, alpha, eps).step() (algo/a2c_acktr.py:30-31,
+ * 74-78) on the flat buffer, after ppo_grad_sumsq filled `partials`: coef = min(1,
+ * max_norm / (total + 1e-6)) (max_norm <= 0: no clipping), grads = grads * scale *
+ * coef, then torch's single-tensor RMSprop without momentum, centering or weight decay:
+ *   sq = sq * alpha;  sq = sq + ((1 - alpha) * g) * g;  p = p + (-lr) * (g / (sqrt(sq) + eps))
+ * one fp32 rounding per operation.  Guards and *skipped as ppo_clip_adam_guarded: a
+ * skipped step leaves params, grads and square_avg bit-unchanged. */
+int ppo_clip_rmsprop_guarded(float* params, float* grads, float* square_avg, long long n, const double* partials,
+                             float scale, double max_norm, double lr, double alpha, double eps, double* norm_out,
+                             const int* guard_i, const double* guard_d, int* skipped, void* stream);
 
 #ifdef __cplusplus
 }

@@ -70,16 +70,19 @@ class _Workspace:
         return t
 
 
-# What tells the three heads kernel families apart on the host: the entry points, whether
+# What tells the three heads kernel families apart on the host: the entry points (train:
+# PPO's row loss, train_a2c: A2C's, same kernels and partials), whether
 # DiagGaussian's logstd (parameter LS; its gradient doubles the bias partials) is passed
 # after BA, and the action dtype.  Bernoulli's partials have Categorical's layouts, so
 # ppo_heads_reduce sums both.
-_HeadKind = collections.namedtuple("_HeadKind", "act train reduce ls dtype")
+_HeadKind = collections.namedtuple("_HeadKind", "act train train_a2c reduce ls dtype")
 _HEADS = {
-    "cat": _HeadKind("ppo_heads_act", "ppo_heads_train", "ppo_heads_reduce", False, torch.int64),
-    "gauss": _HeadKind("ppo_heads_gauss_act", "ppo_heads_gauss_train", "ppo_heads_gauss_reduce", True,
-                       torch.float32),
-    "bern": _HeadKind("ppo_heads_bern_act", "ppo_heads_bern_train", "ppo_heads_reduce", False, torch.float32),
+    "cat": _HeadKind("ppo_heads_act", "ppo_heads_train", "ppo_heads_train_a2c", "ppo_heads_reduce", False,
+                     torch.int64),
+    "gauss": _HeadKind("ppo_heads_gauss_act", "ppo_heads_gauss_train", "ppo_heads_gauss_train_a2c",
+                       "ppo_heads_gauss_reduce", True, torch.float32),
+    "bern": _HeadKind("ppo_heads_bern_act", "ppo_heads_bern_train", "ppo_heads_bern_train_a2c", "ppo_heads_reduce",
+                      False, torch.float32),
 }
 
 
@@ -256,16 +259,22 @@ class _Engine:
         part_b = ws.get("part_b", nblk * (1 + (2 * A if kind.ls else A)), device=dev)
         part_l = ws.get("part_l", nblk * 4, device=dev)
         inv_b = 1.0 / B
-        clipped = int(hp["use_clipped_value_loss"])
+        a2c = hp.get("loss") == "a2c"   # A2C_ACKTR.update: adv is None, the kernel forms returns - value itself
+        clipped = 0 if a2c else int(hp["use_clipped_value_loss"])
         if self.float_actions and storage.actions.shape[-1] != A:
             raise RuntimeError(f"storage holds {storage.actions.shape[-1]} action dimensions, the policy {A}")
         actions = (ptr(storage.actions, kind.dtype, "storage.actions") if self.float_actions
                    else storage.actions.data_ptr())
-        call(kind.train, feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC), self.pv(self.BC), self.pv(self.WA),
-             self.pv(self.BA), *((self.pv(self.LS),) if kind.ls else ()), A, idx.data_ptr(), 0, actions,
-             storage.action_log_probs.data_ptr(), adv.data_ptr(), storage.value_preds.data_ptr(),
-             storage.returns.data_ptr(), hp["clip"], hp["value_coef"], hp["entropy_coef"], inv_b, clipped,
-             int(feat_act), dfeat.data_ptr(), ptr(dfeat_v), part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), s)
+        # what the row loss reads of the storage and its hyper-parameters: PPO's old log-probs,
+        # advantages, value predictions, returns, clip and clipped-value flag; A2C's returns
+        planes = ((storage.returns.data_ptr(),) if a2c else
+                  (storage.action_log_probs.data_ptr(), adv.data_ptr(), storage.value_preds.data_ptr(),
+                   storage.returns.data_ptr(), hp["clip"]))
+        call(kind.train_a2c if a2c else kind.train, feat.data_ptr(), ptr(feat_v), B, H, self.pv(self.WC),
+             self.pv(self.BC), self.pv(self.WA), self.pv(self.BA), *((self.pv(self.LS),) if kind.ls else ()), A,
+             idx.data_ptr(), 0, actions, *planes, hp["value_coef"], hp["entropy_coef"], inv_b,
+             *(() if a2c else (clipped,)), int(feat_act), dfeat.data_ptr(), ptr(dfeat_v), part_w.data_ptr(),
+             part_b.data_ptr(), part_l.data_ptr(), s)
         # ppo_heads_gauss_reduce also writes logstd's gradient and takes no clipped-value flag
         call(kind.reduce, part_w.data_ptr(), part_b.data_ptr(), part_l.data_ptr(), nblk, H, A,
              self.gv(self.WC), self.gv(self.BC), self.gv(self.WA), self.gv(self.BA),

@@ -124,6 +124,13 @@ SIGNATURES = {
                            c_p, c_p, c_p],
     "ppo_heads_bern_train": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_p, c_p, c_p,
                              c_f, c_f, c_f, c_f, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
+    # the train entry points with A2C's row loss: no old_logp / adv / vpred planes, no clip, no clipped-value flag
+    "ppo_heads_train_a2c": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_f, c_f, c_f,
+                            c_int, c_p, c_p, c_p, c_p, c_p, c_p],
+    "ppo_heads_gauss_train_a2c": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_f,
+                                  c_f, c_f, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
+    "ppo_heads_bern_train_a2c": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ll, c_p, c_p, c_f, c_f, c_f,
+                                 c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     # the act entry points with the sampling counter as a device word (c_p where the by-value
     # functions take c_ull), and the launch that advances the word
     "ppo_heads_act_dc": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_ull, c_p, c_int, c_p, c_p, c_p,
@@ -142,6 +149,7 @@ SIGNATURES = {
     "ppo_clip_adam": [c_p, c_p, c_p, c_p, c_ll, c_p, c_f, c_d, c_d, c_d, c_d, c_d, c_ll, c_p, c_p],
     "ppo_clip_adam_guarded": [c_p, c_p, c_p, c_p, c_ll, c_p, c_f, c_d, c_d, c_d, c_d, c_d, c_ll, c_p, c_p, c_p, c_p,
                               c_p],
+    "ppo_clip_rmsprop_guarded": [c_p, c_p, c_p, c_ll, c_p, c_f, c_d, c_d, c_d, c_d, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"ppo_last_error": ctypes.c_char_p, "ppo_packed_weights_size": c_ll, "ppo_fc_fwd_ws_bytes": c_ll}
 # functions whose int return value is a result, not a status

@@ -7,8 +7,8 @@ and `torch.load(path)`.  That still works here (Policy drops its engine when
 pickled), but torch >= 2.6 refuses such a file unless it is loaded with
 weights_only=False, which executes code from the file.  save_checkpoint writes
 plain tensors and builtins instead — loadable with torch.load(weights_only=True)
-— and adds what the reference drops: the optimizer state (Adam moments, step
-count, lr) so a resumed run continues bit-identically.
+— and adds what the reference drops: the optimizer state (PPO: Adam moments, A2C:
+RMSprop's square_avg; step count, lr) so a resumed run continues bit-identically.
 
     save_checkpoint(path, actor_critic, ob_rms, agent=agent)
     actor_critic, ob_rms = load_checkpoint(path, device, agent=agent)
@@ -56,6 +56,12 @@ class RunningMeanStd(object):
         self.mean, self.var, self.count = mean, var, count
 
 
+def _optimizer_kind(opt):
+    """the "kind" of a checkpoint's optimizer block: "adam" (FlatAdam: exp_avg, exp_avg_sq) or
+    "rmsprop" (FlatRMSprop: square_avg); a block without one is Adam's"""
+    return {"FlatAdam": "adam", "FlatRMSprop": "rmsprop"}[type(opt).__name__]
+
+
 def policy_config(actor_critic):
     """Constructor arguments of a Policy (model.py:16), recorded so load can rebuild it."""
     base = actor_critic.base
@@ -77,12 +83,13 @@ def save_checkpoint(path, actor_critic, ob_rms=None, agent=None, extra=None):
           "policy": {k: v.detach().cpu().clone() for k, v in actor_critic.state_dict().items()},
           "ob_rms": _ob_rms_state(ob_rms), "optimizer": None, "extra": extra}
     if agent is not None:
-        sd = agent.optimizer.state_dict()
-        ck["optimizer"] = {"step": int(sd["step"]),
-                           "exp_avg": None if sd["exp_avg"] is None else sd["exp_avg"].detach().cpu().clone(),
-                           "exp_avg_sq": None if sd["exp_avg_sq"] is None else sd["exp_avg_sq"].detach().cpu().clone(),
+        opt = agent.optimizer
+        sd = opt.state_dict()
+        ck["optimizer"] = {"kind": _optimizer_kind(opt), "step": int(sd["step"]),
                            "param_groups": [{k: (list(v) if isinstance(v, tuple) else v)
                                              for k, v in sd["param_groups"][0].items()}]}
+        for k in opt.STATE:   # Adam: exp_avg, exp_avg_sq; RMSprop: square_avg
+            ck["optimizer"][k] = None if sd[k] is None else sd[k].detach().cpu().clone()
     tmp = path + ".tmp"
     torch.save(ck, tmp)
     os.replace(tmp, path)   # a crash mid-save never leaves a truncated checkpoint behind
@@ -124,12 +131,17 @@ def load_checkpoint(path, device=None, actor_critic=None, agent=None):
     ob_rms = None if ob is None else RunningMeanStd(ob["mean"].numpy(), ob["var"].numpy(), ob["count"].item())
     if agent is not None and ck["optimizer"] is not None:
         o = ck["optimizer"]
+        opt = agent.optimizer
+        kind, want = o.get("kind", "adam"), _optimizer_kind(opt)   # no "kind": a file from before RMSprop
+        if kind != want:
+            raise ValueError("%s: holds %s optimizer state, the agent trains with %s "
+                             "(PPO trains with adam, A2C with rmsprop)" % (path, kind, want))
         dev = next(actor_critic.parameters()).device
         pg = dict(o["param_groups"][0])
-        pg["betas"] = tuple(pg["betas"])
-        agent.optimizer.load_state_dict({
-            "step": o["step"],
-            "exp_avg": None if o["exp_avg"] is None else o["exp_avg"].to(dev),
-            "exp_avg_sq": None if o["exp_avg_sq"] is None else o["exp_avg_sq"].to(dev),
-            "param_groups": [pg]})
+        if "betas" in pg:
+            pg["betas"] = tuple(pg["betas"])
+        sd = {"step": o["step"], "param_groups": [pg]}
+        for k in opt.STATE:
+            sd[k] = None if o[k] is None else o[k].to(dev)
+        opt.load_state_dict(sd)
     return actor_critic, ob_rms

@@ -135,9 +135,10 @@ struct TrainArgs {
   const int64_t* idx;      // storage row of each sample (nullable: row0 + b)
   long long row0;
   const int64_t* actions;  // storage planes, indexed by storage row
-  const float *old_logp, *adv, *vpred, *ret;
+  const float *old_logp, *adv, *vpred, *ret;   // LOSS_A2C reads only ret; the other three may be NULL
   float clip, value_coef, entropy_coef, inv_b;
   int use_clipped_value_loss;
+  int loss_kind;           // LOSS_PPO | LOSS_A2C (heads_common.h)
   int feat_act;            // activation producing the features: 0 none (GRU), 1 ReLU, 2 tanh
   float* dfeat;            // [B][H] dL/d(feature pre-activation) (both heads when dfeat_v is NULL)
   float* dfeat_v;          // [B][H] critic-branch gradient (MLPBase) or NULL
@@ -151,9 +152,11 @@ struct TrainArgs {
 // and the GRU policy): every per-lane and per-action bound is a compile-time
 // constant, which removes the uniform branches around each unrolled operation
 // (the generic instantiation runs ~2,500 instructions per row).
-template <int HC, int AMAX, bool FAST>
+// LK: LOSS_RT, or the loss kind fixed at compile time (split_loss, heads_common.h).
+template <int HC, int AMAX, bool FAST, int LK>
 __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int loss_kind = loss_kind_of<LK>(a.loss_kind);
   const int H = FAST ? 64 * HC : a.H, A = FAST ? AMAX : a.A;
   const float* const feat_v = FAST ? nullptr : a.feat_v;
   float* const dfeat_v = FAST ? nullptr : a.dfeat_v;
@@ -182,9 +185,11 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
   if (lane < a.rows_per_wave && r0 + lane < a.B) {
     const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
     q_act = action_index(a.actions[sr], A);
-    q_adv = a.adv[sr];
-    q_olp = a.old_logp[sr];
-    q_vo = a.vpred[sr];
+    if (loss_kind != LOSS_A2C) {   // A2C: the three pointers may be NULL
+      q_adv = a.adv[sr];
+      q_olp = a.old_logp[sr];
+      q_vo = a.vpred[sr];
+    }
     q_ret = a.ret[sr];
   }
   auto bcast = [](float x, int j) {
@@ -221,33 +226,39 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
       if (o == act) lp = nl[o];
       if (o < A) ent -= nl[o] * p[o];
     }
-    // action loss (ppo.py:61-66)
-    const float adv = bcast(q_adv, rr);
-    const float ratio = expf(lp - bcast(q_olp, rr));
-    const float surr1 = ratio * adv;
-    const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-    const float surr2 = rc * adv;
-    const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-    const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-    const float g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-    // value loss (ppo.py:68-77)
-    const float vo = bcast(q_vo, rr), R = bcast(q_ret, rr);
-    float g_v, vl_row;
-    if (a.use_clipped_value_loss) {
-      const float dv = value - vo;
-      const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-      const float l1 = (value - R) * (value - R);
-      const float l2 = (vpc - R) * (vpc - R);
-      vl_row = fmaxf(l1, l2);
-      const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-      const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-      g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+    const float R = bcast(q_ret, rr);
+    float g_logp, g_v;
+    if (loss_kind == LOSS_A2C) {
+      a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
     } else {
-      vl_row = (R - value) * (R - value);
-      g_v = a.value_coef * a.inv_b * (value - R);
+      // action loss (ppo.py:61-66)
+      const float adv = bcast(q_adv, rr);
+      const float ratio = expf(lp - bcast(q_olp, rr));
+      const float surr1 = ratio * adv;
+      const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
+      const float surr2 = rc * adv;
+      const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
+      const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
+      g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+      // value loss (ppo.py:68-77)
+      const float vo = bcast(q_vo, rr);
+      float vl_row;
+      if (a.use_clipped_value_loss) {
+        const float dv = value - vo;
+        const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
+        const float l1 = (value - R) * (value - R);
+        const float l2 = (vpc - R) * (vpc - R);
+        vl_row = fmaxf(l1, l2);
+        const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
+        const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
+        g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+      } else {
+        vl_row = (R - value) * (R - value);
+        g_v = a.value_coef * a.inv_b * (value - R);
+      }
+      s_vl += vl_row;
+      s_al += fminf(surr1, surr2);
     }
-    s_vl += vl_row;
-    s_al += fminf(surr1, surr2);
     s_ent += ent;
     // dL/dlogits = g_logp (onehot - p) + (c_e/B) p (nl + H)
     float gz[AMAX];
@@ -357,9 +368,11 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
   if (lane < a.rows_per_wave && r0 + lane < a.B) {
     const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
     q_act = action_index(a.actions[sr], A);
-    q_adv = a.adv[sr];
-    q_olp = a.old_logp[sr];
-    q_vo = a.vpred[sr];
+    if (a.loss_kind != LOSS_A2C) {   // A2C: the three pointers may be NULL
+      q_adv = a.adv[sr];
+      q_olp = a.old_logp[sr];
+      q_vo = a.vpred[sr];
+    }
     q_ret = a.ret[sr];
   }
   auto bcast = [](float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); };
@@ -400,33 +413,39 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
       if (o == act) lp = nl[o];
       ent -= nl[o] * p[o];
     }
-    // action loss (ppo.py:61-66)
-    const float adv = bcast(q_adv, rr);
-    const float ratio = expf(lp - bcast(q_olp, rr));
-    const float surr1 = ratio * adv;
-    const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-    const float surr2 = rc * adv;
-    const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-    const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-    const float g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-    // value loss (ppo.py:68-77)
-    const float vo = bcast(q_vo, rr), R = bcast(q_ret, rr);
-    float g_v, vl_row;
-    if (a.use_clipped_value_loss) {
-      const float dv = value - vo;
-      const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-      const float l1 = (value - R) * (value - R);
-      const float l2 = (vpc - R) * (vpc - R);
-      vl_row = fmaxf(l1, l2);
-      const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-      const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-      g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+    const float R = bcast(q_ret, rr);
+    float g_logp, g_v;
+    if (a.loss_kind == LOSS_A2C) {
+      a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
     } else {
-      vl_row = (R - value) * (R - value);
-      g_v = a.value_coef * a.inv_b * (value - R);
+      // action loss (ppo.py:61-66)
+      const float adv = bcast(q_adv, rr);
+      const float ratio = expf(lp - bcast(q_olp, rr));
+      const float surr1 = ratio * adv;
+      const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
+      const float surr2 = rc * adv;
+      const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
+      const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
+      g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+      // value loss (ppo.py:68-77)
+      const float vo = bcast(q_vo, rr);
+      float vl_row;
+      if (a.use_clipped_value_loss) {
+        const float dv = value - vo;
+        const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
+        const float l1 = (value - R) * (value - R);
+        const float l2 = (vpc - R) * (vpc - R);
+        vl_row = fmaxf(l1, l2);
+        const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
+        const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
+        g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+      } else {
+        vl_row = (R - value) * (R - value);
+        g_v = a.value_coef * a.inv_b * (value - R);
+      }
+      s_vl += vl_row;
+      s_al += fminf(surr1, surr2);
     }
-    s_vl += vl_row;
-    s_al += fminf(surr1, surr2);
     s_ent += ent;
     float g[9];   // g[0] = dL/dvalue, g[1 + o] = dL/dlogit o
     g[0] = g_v;
@@ -569,6 +588,24 @@ int heads_act(const char* name, const ActCall& c, void* stream) {
 // that kernel would race with the blocks that have not read the word yet
 __global__ void rng_advance_kernel(unsigned long long* counter, unsigned long long by) { *counter += by; }
 
+// the instantiations built once per loss kind instead of with the run-time branch
+// (heads_common.h, LOSS_RT): 96 -> 100, 165 -> 169 and 253 -> 257 VGPRs with it
+constexpr bool split_loss(int HC, int AMAX, bool FAST) {
+  return AMAX == 8 && ((HC == 1 && FAST) || (HC == 4 && !FAST) || (HC == 8 && !FAST));
+}
+
+template <int HC, int AMAX, bool FAST>
+void launch_train_reg(const TrainArgs& a, int blocks, hipStream_t st) {
+  if constexpr (split_loss(HC, AMAX, FAST)) {
+    if (a.loss_kind == LOSS_A2C)
+      heads_train_kernel<HC, AMAX, FAST, LOSS_A2C><<<blocks, 64 * HW, 0, st>>>(a);
+    else
+      heads_train_kernel<HC, AMAX, FAST, LOSS_PPO><<<blocks, 64 * HW, 0, st>>>(a);
+  } else {
+    heads_train_kernel<HC, AMAX, FAST, LOSS_RT><<<blocks, 64 * HW, 0, st>>>(a);
+  }
+}
+
 template <int HC, int AMAX>
 int launch_train(const TrainArgs& a, int blocks, hipStream_t st) {
   // ppo_tune_set("heads_lds", 0): the register-weight kernel (A/B)
@@ -579,9 +616,9 @@ int launch_train(const TrainArgs& a, int blocks, hipStream_t st) {
     return 0;
   }
   if (a.A == AMAX && a.H == 64 * HC && !a.feat_v && !a.dfeat_v)
-    heads_train_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(a);
+    launch_train_reg<HC, AMAX, true>(a, blocks, st);
   else
-    heads_train_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(a);
+    launch_train_reg<HC, AMAX, false>(a, blocks, st);
   PPO_LAUNCH_CHECK("heads_train_kernel");
   return 0;
 }
@@ -641,6 +678,25 @@ PPO_API int ppo_heads_train_blocks(int B) {
   return (int)ceil_div(B, HW * rpw);
 }
 
+namespace {
+
+// ppo_heads_train / ppo_heads_train_a2c: one argument check, launch shape and kernel
+// selection; the entry points differ in the row loss and in the storage planes it reads
+int heads_train(const char* name, TrainArgs a, void* stream) {
+  PPO_REQUIRE(a.B > 0 && a.A >= 1 && a.A <= 16, "%s: B=%d A=%d", name, a.B, a.A);
+  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
+  ProfScope prof("heads_train", as_stream(stream),
+                 (double)a.B * (8.0 * a.H * (a.feat_v ? 2 : 1) + (a.idx ? 8.0 : 0.0) +
+                                (a.loss_kind == LOSS_A2C ? 20.0 : 32.0)));
+  a.rows_per_wave = 32;
+  const int blocks = ppo_heads_train_blocks(a.B);
+  hipStream_t st = as_stream(stream);
+  if (a.A <= 8) return dispatch_train<8>(hc_of(a.H), a, blocks, st);
+  return dispatch_train<16>(hc_of(a.H), a, blocks, st);
+}
+
+}  // namespace
+
 PPO_API int ppo_heads_train(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
                             const float* wa,
                             const float* ba, int A, const int64_t* idx, long long row0, const int64_t* actions,
@@ -648,26 +704,42 @@ PPO_API int ppo_heads_train(const float* feat, const float* feat_v, int B, int H
                             float value_coef, float entropy_coef, float inv_b, int use_clipped_value_loss,
                             int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
                             float* part_loss, void* stream) {
-  PPO_REQUIRE(B > 0 && A >= 1 && A <= 16, "ppo_heads_train: B=%d A=%d", B, A);
-  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_train: hidden size %d (1..512)", H);
-  ProfScope prof("heads_train", as_stream(stream),
-                 (double)B * (8.0 * H * (feat_v ? 2 : 1) + (idx ? 8.0 : 0.0) + 32.0));
   TrainArgs a;
   a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
   a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = old_logp; a.adv = adv; a.vpred = vpred; a.ret = ret;
   a.clip = clip; a.value_coef = value_coef; a.entropy_coef = entropy_coef; a.inv_b = inv_b;
   a.use_clipped_value_loss = use_clipped_value_loss;
+  a.loss_kind = LOSS_PPO;
   a.feat_act = feat_act;
   a.dfeat_v = dfeat_v;
   a.dfeat = dfeat; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  a.rows_per_wave = 32;
-  const int blocks = ppo_heads_train_blocks(B);
-  hipStream_t st = as_stream(stream);
-  if (A <= 8) return dispatch_train<8>(hc_of(H), a, blocks, st);
-  return dispatch_train<16>(hc_of(H), a, blocks, st);
+  return heads_train("ppo_heads_train", a, stream);
 }
 
-// Σ over the heads_train blocks (fixed order) -> head gradients; losses -> loss_acc
+// ppo_heads_train with A2C's row loss (algo/a2c_acktr.py:48-51, a2c_row_loss): reads only
+// the actions and the returns of the storage.  part_loss slot 0 holds Σ 2 (R - v)^2, so
+// ppo_heads_reduce's 0.5·Σ/B is mean((R - v)^2); slot 1 holds Σ adv·logp.
+PPO_API int ppo_heads_train_a2c(const float* feat, const float* feat_v, int B, int H, const float* wc,
+                                const float* bc, const float* wa, const float* ba, int A, const int64_t* idx,
+                                long long row0, const int64_t* actions, const float* ret, float value_coef,
+                                float entropy_coef, float inv_b, int feat_act, float* dfeat, float* dfeat_v,
+                                float* part_w, float* part_b, float* part_loss, void* stream) {
+  TrainArgs a;
+  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
+  a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = nullptr; a.adv = nullptr; a.vpred = nullptr;
+  a.ret = ret;
+  a.clip = 0.f; a.value_coef = value_coef; a.entropy_coef = entropy_coef; a.inv_b = inv_b;
+  a.use_clipped_value_loss = 0;
+  a.loss_kind = LOSS_A2C;
+  a.feat_act = feat_act;
+  a.dfeat_v = dfeat_v;
+  a.dfeat = dfeat; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
+  return heads_train("ppo_heads_train_a2c", a, stream);
+}
+
+// Σ over the heads_train blocks (fixed order) -> head gradients; losses -> loss_acc.
+// part_loss slot 0 is halved (0.5·Σ/B): PPO's kernels store Σ of the row's squared error
+// there, the A2C launches Σ 2 (R - v)^2, so both come out as their algorithm's value loss
 PPO_API int ppo_heads_reduce(const float* part_w, const float* part_b, const float* part_loss, int nblk, int H, int A,
                              float* g_wc, float* g_bc, float* g_wa, float* g_ba, double* loss_acc, double inv_b,
                              float scale, int use_clipped_value_loss, void* stream) {

@@ -64,7 +64,42 @@ __device__ __forceinline__ float act_grad(float d, float y, int act) {
   return d;
 }
 
+// The row loss a train launch computes: the `loss_kind` field of the three *TrainArgs
+// structs, a run-time flag like use_clipped_value_loss (wave-uniform branch, no
+// instantiation doubled).
+constexpr int LOSS_PPO = 0;   // clipped surrogate + (clipped) value loss  algo/ppo.py:61-81
+constexpr int LOSS_A2C = 1;   // policy gradient + squared error           algo/a2c_acktr.py:48-51
+// The register-weight train kernels take the kind as a last template argument LK as well:
+// LOSS_RT reads the field (the branch above), a fixed kind compiles the other loss out.
+// A few instantiations sit on a VGPR occupancy step, and the branch's three or four extra
+// registers pushed them over it; those (each file's split_loss) are built once per kind
+// instead, which leaves their PPO code what it was without the branch.
+constexpr int LOSS_RT = -1;
+
+template <int LK>
+__device__ __forceinline__ int loss_kind_of(int field) {
+  return LK == LOSS_RT ? field : LK;
+}
+
+// A2C's row loss (algo/a2c_acktr.py:48-51, 71-72) from the row's value v, log-prob lp
+// and stored return R:
+//   adv = R - v (one fp32 subtraction; detached, so no gradient reaches v through it)
+//   value loss  (R - v)^2 .mean()      -> g_v    = value_coef · inv_b · 2 (v - R)   (no 0.5 in A2C)
+//   action loss -(adv · lp).mean()     -> g_logp = -inv_b · adv
+// The loss partials go through the reduce PPO uses (loss_reduce_kernel: 0.5·Σ/B, -Σ/B), so
+// slot 0 accumulates 2 (R - v)^2 (the doubling is exact in fp32) and slot 1 adv · lp.
+// Neither old_logp, the stored advantage nor the stored value prediction is used.
+__device__ __forceinline__ void a2c_row_loss(float v, float lp, float R, float value_coef, float inv_b,
+                                             float& g_logp, float& g_v, float& s_vl, float& s_al) {
+  const float adv = R - v;
+  g_logp = -inv_b * adv;
+  g_v = value_coef * inv_b * (2.f * (v - R));
+  s_vl += 2.f * (adv * adv);
+  s_al += adv * lp;
+}
+
 // loss partials -> acc[0..3] += {0.5·Σvl/B, -Σal/B, Σent/B, # bad actions} (double, fixed order)
+// (slot 0 of a LOSS_A2C launch holds Σ 2 (R - v)^2, so 0.5·Σ/B is mean((R - v)^2) there)
 __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ part_loss, int nblk,
                                                           double* __restrict__ loss_acc, double inv_b) {
   __shared__ double r[4][256];

@@ -161,9 +161,10 @@ struct GaussTrainArgs {
   const int64_t* idx;      // storage row of each sample (nullable: row0 + b)
   long long row0;
   const float* actions;    // storage plane [row][A]
-  const float *old_logp, *adv, *vpred, *ret;
+  const float *old_logp, *adv, *vpred, *ret;   // LOSS_A2C reads only ret; the other three may be NULL
   float clip, value_coef, entropy_coef, inv_b;
   int use_clipped_value_loss;
+  int loss_kind;           // LOSS_PPO | LOSS_A2C (heads_common.h)
   int feat_act;            // activation producing the features: 0 none (GRU), 1 ReLU, 2 tanh
   float* dfeat;            // [B][H]
   float* dfeat_v;          // [B][H] critic-branch gradient (MLPBase) or NULL
@@ -177,14 +178,16 @@ struct GaussTrainArgs {
 struct RowScalars {
   float adv = 0.f, olp = 0.f, vo = 0.f, ret = 0.f;
   int sr_lo = 0, sr_hi = 0;   // storage row (the action plane is read per row, one row ahead)
-  __device__ __forceinline__ void load(const GaussTrainArgs& a, long long r0, int lane) {
+  __device__ __forceinline__ void load(const GaussTrainArgs& a, int loss_kind, long long r0, int lane) {
     if (lane < a.rows_per_wave && r0 + lane < a.B) {
       const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
       sr_lo = (int)(sr & 0xffffffffll);
       sr_hi = (int)(sr >> 32);
-      adv = a.adv[sr];
-      olp = a.old_logp[sr];
-      vo = a.vpred[sr];
+      if (loss_kind != LOSS_A2C) {   // A2C: the three pointers may be NULL
+        adv = a.adv[sr];
+        olp = a.old_logp[sr];
+        vo = a.vpred[sr];
+      }
       ret = a.ret[sr];
     }
   }
@@ -203,7 +206,7 @@ __device__ __forceinline__ float bcast(float x, int j) {
 // ratio / clip / surrogate and the value loss exactly as heads_train_kernel, then
 // dL/dmu and the row's dL/dlogstd term added to gs.
 template <int AMAX>
-__device__ __forceinline__ void gauss_row(const GaussTrainArgs& a, int A, const GaussC<AMAX>& gc, float value,
+__device__ __forceinline__ void gauss_row(const GaussTrainArgs& a, int loss_kind, int A, const GaussC<AMAX>& gc, float value,
                                           const float (&mu)[AMAX], const float (&act)[AMAX], float adv, float olp,
                                           float vo, float R, float& g_v, float (&gmu)[AMAX], float (&gs)[AMAX],
                                           float& s_vl, float& s_al, float& s_bad) {
@@ -214,31 +217,36 @@ __device__ __forceinline__ void gauss_row(const GaussTrainArgs& a, int A, const 
     if (o < A) bad |= !__builtin_isfinite(act[o]);
   s_bad += bad ? 1.f : 0.f;   // counted; PPO.update raises
   const float lp = gauss_logp(gc, mu, act, A);
-  // action loss (ppo.py:61-66)
-  const float ratio = expf(lp - olp);
-  const float surr1 = ratio * adv;
-  const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-  const float surr2 = rc * adv;
-  const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-  const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-  const float g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-  // value loss (ppo.py:68-77)
-  float vl_row;
-  if (a.use_clipped_value_loss) {
-    const float dv = value - vo;
-    const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-    const float l1 = (value - R) * (value - R);
-    const float l2 = (vpc - R) * (vpc - R);
-    vl_row = fmaxf(l1, l2);
-    const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-    const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-    g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+  float g_logp;
+  if (loss_kind == LOSS_A2C) {
+    a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
   } else {
-    vl_row = (R - value) * (R - value);
-    g_v = a.value_coef * a.inv_b * (value - R);
+    // action loss (ppo.py:61-66)
+    const float ratio = expf(lp - olp);
+    const float surr1 = ratio * adv;
+    const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
+    const float surr2 = rc * adv;
+    const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
+    const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
+    g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+    // value loss (ppo.py:68-77)
+    float vl_row;
+    if (a.use_clipped_value_loss) {
+      const float dv = value - vo;
+      const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
+      const float l1 = (value - R) * (value - R);
+      const float l2 = (vpc - R) * (vpc - R);
+      vl_row = fmaxf(l1, l2);
+      const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
+      const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
+      g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+    } else {
+      vl_row = (R - value) * (R - value);
+      g_v = a.value_coef * a.inv_b * (value - R);
+    }
+    s_vl += vl_row;
+    s_al += fminf(surr1, surr2);
   }
-  s_vl += vl_row;
-  s_al += fminf(surr1, surr2);
 #pragma unroll
   for (int o = 0; o < AMAX; ++o) {
     if (o < A) {
@@ -289,9 +297,11 @@ __device__ __forceinline__ void gauss_store_scalars(const GaussTrainArgs& a, int
 }
 
 // FAST: A == AMAX, H == 64·HC, no separate critic features / gradient
-template <int HC, int AMAX, bool FAST>
+// LK: LOSS_RT, or the loss kind fixed at compile time (split_loss, heads_common.h)
+template <int HC, int AMAX, bool FAST, int LK>
 __global__ __launch_bounds__(64 * HW) void gauss_train_kernel(const GaussTrainArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int loss_kind = loss_kind_of<LK>(a.loss_kind);
   const int H = FAST ? 64 * HC : a.H, A = FAST ? AMAX : a.A;
   const float* const feat_v = FAST ? nullptr : a.feat_v;
   float* const dfeat_v = FAST ? nullptr : a.dfeat_v;
@@ -312,7 +322,7 @@ __global__ __launch_bounds__(64 * HW) void gauss_train_kernel(const GaussTrainAr
   float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
   const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
   RowScalars q;
-  q.load(a, r0, lane);
+  q.load(a, loss_kind, r0, lane);
   // features and the row's A action floats (lane o holds dimension o) one row ahead
   float fn[HC], fvn[HC], an = 0.f;
   auto load_row = [&](int rr) {
@@ -345,7 +355,7 @@ __global__ __launch_bounds__(64 * HW) void gauss_train_kernel(const GaussTrainAr
 #pragma unroll
     for (int o = 0; o < AMAX; ++o) act[o] = bcast(acur, o);
     float g_v, gmu[AMAX];
-    gauss_row(a, A, gc, value, mu, act, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g_v,
+    gauss_row(a, loss_kind, A, gc, value, mu, act, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g_v,
               gmu, gs, s_vl, s_al, s_bad);
     s_ent += gc.ent;
     // dL/dh for this lane's columns, through the features' activation; head grads
@@ -424,7 +434,7 @@ __global__ __launch_bounds__(64 * HW) void gauss_train_lds_kernel(const GaussTra
   float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
   const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
   RowScalars q;
-  q.load(a, r0, lane);
+  q.load(a, a.loss_kind, r0, lane);
   f32x4 fn[2];
   float an = 0.f;
   auto load_row = [&](int rr) {
@@ -464,7 +474,7 @@ __global__ __launch_bounds__(64 * HW) void gauss_train_lds_kernel(const GaussTra
       act[o] = bcast(acur, o);
     }
     float g[9], gmu[A];   // g[0] = dL/dvalue, g[1 + o] = dL/dmu_o
-    gauss_row(a, A, gc, value, mu, act, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g[0],
+    gauss_row(a, a.loss_kind, A, gc, value, mu, act, bcast(q.adv, rr), bcast(q.olp, rr), bcast(q.vo, rr), bcast(q.ret, rr), g[0],
               gmu, gs, s_vl, s_al, s_bad);
     s_ent += gc.ent;
 #pragma unroll
@@ -535,6 +545,22 @@ int dispatch_act(int HC, const ActArgs& a, hipStream_t st) {
   return PPO_EARG;
 }
 
+// the instantiation built once per loss kind instead of with the run-time branch
+// (heads_common.h, LOSS_RT)
+constexpr bool split_loss(int HC, int AMAX, bool FAST) { return AMAX == 8 && HC == 1 && !FAST; }
+
+template <int HC, int AMAX, bool FAST>
+void launch_train_reg(const GaussTrainArgs& a, int blocks, hipStream_t st) {
+  if constexpr (split_loss(HC, AMAX, FAST)) {
+    if (a.loss_kind == LOSS_A2C)
+      gauss_train_kernel<HC, AMAX, FAST, LOSS_A2C><<<blocks, 64 * HW, 0, st>>>(a);
+    else
+      gauss_train_kernel<HC, AMAX, FAST, LOSS_PPO><<<blocks, 64 * HW, 0, st>>>(a);
+  } else {
+    gauss_train_kernel<HC, AMAX, FAST, LOSS_RT><<<blocks, 64 * HW, 0, st>>>(a);
+  }
+}
+
 template <int HC, int AMAX>
 int launch_train(const GaussTrainArgs& a, int blocks, hipStream_t st) {
   if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
@@ -544,9 +570,9 @@ int launch_train(const GaussTrainArgs& a, int blocks, hipStream_t st) {
     return 0;
   }
   if (a.A == AMAX && a.H == 64 * HC && !a.feat_v && !a.dfeat_v)
-    gauss_train_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(a);
+    launch_train_reg<HC, AMAX, true>(a, blocks, st);
   else
-    gauss_train_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(a);
+    launch_train_reg<HC, AMAX, false>(a, blocks, st);
   PPO_LAUNCH_CHECK("gauss_train_kernel");
   return 0;
 }
@@ -574,6 +600,20 @@ int gauss_act(const char* name, ActArgs a, void* stream) {
   a.rows_per_wave = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(a.N, 4096)));
   if (a.A <= 8) return dispatch_act<8>(hc_of(a.H), a, as_stream(stream));
   return dispatch_act<16>(hc_of(a.H), a, as_stream(stream));
+}
+
+// ppo_heads_gauss_train / ppo_heads_gauss_train_a2c: one argument check, launch shape and
+// kernel selection
+int gauss_train(const char* name, GaussTrainArgs a, void* stream) {
+  PPO_REQUIRE(a.B > 0 && a.A >= 1 && a.A <= 16, "%s: B=%d A=%d", name, a.B, a.A);
+  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
+  ProfScope prof("heads_gauss_train", as_stream(stream),
+                 (double)a.B * (8.0 * a.H * (a.feat_v ? 2 : 1) + (a.idx ? 8.0 : 0.0) +
+                                (a.loss_kind == LOSS_A2C ? 12.0 : 24.0) + 4.0 * a.A));
+  a.rows_per_wave = 32;
+  const int blocks = ppo_heads_train_blocks(a.B);
+  if (a.A <= 8) return dispatch_train<8>(hc_of(a.H), a, blocks, as_stream(stream));
+  return dispatch_train<16>(hc_of(a.H), a, blocks, as_stream(stream));
 }
 
 }  // namespace
@@ -621,20 +661,29 @@ PPO_API int ppo_heads_gauss_train(const float* feat, const float* feat_v, int B,
                                   float value_coef, float entropy_coef, float inv_b, int use_clipped_value_loss,
                                   int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
                                   float* part_loss, void* stream) {
-  PPO_REQUIRE(B > 0 && A >= 1 && A <= 16, "ppo_heads_gauss_train: B=%d A=%d", B, A);
-  PPO_REQUIRE(H > 0 && H <= 512, "ppo_heads_gauss_train: hidden size %d (1..512)", H);
-  ProfScope prof("heads_gauss_train", as_stream(stream),
-                 (double)B * (8.0 * H * (feat_v ? 2 : 1) + (idx ? 8.0 : 0.0) + 24.0 + 4.0 * A));
   GaussTrainArgs a;
   a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
   a.logstd = logstd; a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = old_logp; a.adv = adv;
   a.vpred = vpred; a.ret = ret; a.clip = clip; a.value_coef = value_coef; a.entropy_coef = entropy_coef;
-  a.inv_b = inv_b; a.use_clipped_value_loss = use_clipped_value_loss; a.feat_act = feat_act;
+  a.inv_b = inv_b; a.use_clipped_value_loss = use_clipped_value_loss; a.loss_kind = LOSS_PPO; a.feat_act = feat_act;
   a.dfeat = dfeat; a.dfeat_v = dfeat_v; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  a.rows_per_wave = 32;
-  const int blocks = ppo_heads_train_blocks(B);
-  if (A <= 8) return dispatch_train<8>(hc_of(H), a, blocks, as_stream(stream));
-  return dispatch_train<16>(hc_of(H), a, blocks, as_stream(stream));
+  return gauss_train("ppo_heads_gauss_train", a, stream);
+}
+
+// ppo_heads_gauss_train with A2C's row loss (algo/a2c_acktr.py:48-51, a2c_row_loss): reads
+// only the actions and the returns of the storage; part_loss as ppo_heads_train_a2c
+PPO_API int ppo_heads_gauss_train_a2c(const float* feat, const float* feat_v, int B, int H, const float* wc,
+                                      const float* bc, const float* wa, const float* ba, const float* logstd, int A,
+                                      const int64_t* idx, long long row0, const float* actions, const float* ret,
+                                      float value_coef, float entropy_coef, float inv_b, int feat_act, float* dfeat,
+                                      float* dfeat_v, float* part_w, float* part_b, float* part_loss, void* stream) {
+  GaussTrainArgs a;
+  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
+  a.logstd = logstd; a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = nullptr; a.adv = nullptr;
+  a.vpred = nullptr; a.ret = ret; a.clip = 0.f; a.value_coef = value_coef; a.entropy_coef = entropy_coef;
+  a.inv_b = inv_b; a.use_clipped_value_loss = 0; a.loss_kind = LOSS_A2C; a.feat_act = feat_act;
+  a.dfeat = dfeat; a.dfeat_v = dfeat_v; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
+  return gauss_train("ppo_heads_gauss_train_a2c", a, stream);
 }
 
 // Σ over the gauss_train blocks (fixed order) -> head and logstd gradients; losses -> loss_acc
