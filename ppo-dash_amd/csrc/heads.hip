@@ -19,8 +19,7 @@
 // fc layer: loss terms, dL/dlogits and dL/dvalue (analytic, with autograd's
 // tie conventions), dL/dfeature masked by the fc ReLU, and per-block partial
 // sums of the head weight/bias gradients (deterministic reduce afterwards).
-#include "heads_common.h"   // HW, HeadW, load_head_w, head_dots, act_grad, loss_reduce_kernel, hc_of
-#include "tune.h"
+#include "heads_dispatch.h"   // and through it heads_common.h: HW, HeadW, load_head_w, head_dots, act_grad, ...
 
 namespace {
 
@@ -173,7 +172,6 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
     for (int c = 0; c < HC; ++c) gwa[o][c] = 0.f;
   }
   float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
-  const float clip = a.clip;
   const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
   // The per-row storage scalars (the minibatch gather idx -> action, advantage,
   // old log-prob, value, return) of all of this wave's rows are fetched up
@@ -192,9 +190,6 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
     }
     q_ret = a.ret[sr];
   }
-  auto bcast = [](float x, int j) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
-  };
   float fn[HC], fvn[HC];
   auto load_row = [&](long long row) {
 #pragma unroll
@@ -231,33 +226,8 @@ __global__ __launch_bounds__(64 * HW) void heads_train_kernel(const TrainArgs a)
     if (loss_kind == LOSS_A2C) {
       a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
     } else {
-      // action loss (ppo.py:61-66)
-      const float adv = bcast(q_adv, rr);
-      const float ratio = expf(lp - bcast(q_olp, rr));
-      const float surr1 = ratio * adv;
-      const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-      const float surr2 = rc * adv;
-      const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-      const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-      g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-      // value loss (ppo.py:68-77)
-      const float vo = bcast(q_vo, rr);
-      float vl_row;
-      if (a.use_clipped_value_loss) {
-        const float dv = value - vo;
-        const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-        const float l1 = (value - R) * (value - R);
-        const float l2 = (vpc - R) * (vpc - R);
-        vl_row = fmaxf(l1, l2);
-        const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-        const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-        g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
-      } else {
-        vl_row = (R - value) * (R - value);
-        g_v = a.value_coef * a.inv_b * (value - R);
-      }
-      s_vl += vl_row;
-      s_al += fminf(surr1, surr2);
+      ppo_row_loss(a, value, lp, LaneOf{q_adv, rr}, LaneOf{q_olp, rr}, LaneOf{q_vo, rr}, R, g_logp, g_v, s_vl,
+                   s_al);   // ppo.py:61-77
     }
     s_ent += ent;
     // dL/dlogits = g_logp (onehot - p) + (c_e/B) p (nl + H)
@@ -361,7 +331,6 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
 #pragma unroll
   for (int o = 0; o < A; ++o) gba[o] = 0.f;
   float s_vl = 0.f, s_al = 0.f, s_ent = 0.f, s_bad = 0.f;
-  const float clip = a.clip;
   const long long r0 = ((long long)blockIdx.x * HW + wave) * a.rows_per_wave;
   int q_act = 0;
   float q_adv = 0.f, q_olp = 0.f, q_vo = 0.f, q_ret = 0.f;
@@ -375,7 +344,6 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
     }
     q_ret = a.ret[sr];
   }
-  auto bcast = [](float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); };
   f32x4 fn[2];
   auto load_row = [&](long long row) {
 #pragma unroll
@@ -418,33 +386,8 @@ __global__ __launch_bounds__(64 * HW) void heads_train_lds_kernel(const TrainArg
     if (a.loss_kind == LOSS_A2C) {
       a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
     } else {
-      // action loss (ppo.py:61-66)
-      const float adv = bcast(q_adv, rr);
-      const float ratio = expf(lp - bcast(q_olp, rr));
-      const float surr1 = ratio * adv;
-      const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-      const float surr2 = rc * adv;
-      const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-      const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-      g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-      // value loss (ppo.py:68-77)
-      const float vo = bcast(q_vo, rr);
-      float vl_row;
-      if (a.use_clipped_value_loss) {
-        const float dv = value - vo;
-        const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-        const float l1 = (value - R) * (value - R);
-        const float l2 = (vpc - R) * (vpc - R);
-        vl_row = fmaxf(l1, l2);
-        const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-        const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-        g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
-      } else {
-        vl_row = (R - value) * (R - value);
-        g_v = a.value_coef * a.inv_b * (value - R);
-      }
-      s_vl += vl_row;
-      s_al += fminf(surr1, surr2);
+      ppo_row_loss(a, value, lp, LaneOf{q_adv, rr}, LaneOf{q_olp, rr}, LaneOf{q_vo, rr}, R, g_logp, g_v, s_vl,
+                   s_al);   // ppo.py:61-77
     }
     s_ent += ent;
     float g[9];   // g[0] = dL/dvalue, g[1 + o] = dL/dlogit o
@@ -527,6 +470,10 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ x, 
   if (threadIdx.x == 0) out[0] = (float)(r[0] / (double)n);
 }
 
+// *counter += by, after the act kernel that read it (stream order): an increment inside
+// that kernel would race with the blocks that have not read the word yet
+__global__ void rng_advance_kernel(unsigned long long* counter, unsigned long long by) { *counter += by; }
+
 // the arguments of one act launch (counter_p: the sampling counter as a word in device
 // memory, read by the kernel; NULL: the by-value counter)
 struct ActCall {
@@ -542,97 +489,60 @@ struct ActCall {
   float* v;
   int64_t* act;
   float *lp, *ent;
+  int rows_per_wave;
 };
 
-template <int HC, int AMAX>
-int launch_act(const ActCall& c, hipStream_t st) {
-  // ~4096 waves in flight (4 per SIMD at this kernel's 122-137 VGPRs): a rollout batch of
-  // 4,096 rows takes one row per wave, so no wave runs two rows' dependent chains back to back
-  const int rpw = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(c.N, 4096)));
-  const unsigned blocks = ceil_div(c.N, HW * rpw);
-  if (c.A == AMAX && c.H == 64 * HC && !c.feat_v)
-    heads_act_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(c.feat, c.feat_v, c.N, c.H, c.wc, c.bc, c.wa, c.ba, c.A,
-                                                        c.noise, c.seed, c.counter, c.counter_p, c.det, c.given, c.v,
-                                                        c.act, c.lp, c.ent, rpw);
-  else
-    heads_act_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(c.feat, c.feat_v, c.N, c.H, c.wc, c.bc, c.wa, c.ba, c.A,
+// what heads_dispatch.h needs to know of this family
+struct Cat {
+  using Act = ActCall;
+  using Train = TrainArgs;
+  static constexpr const char* noun = "actions";
+  static constexpr const char *act_scope = "heads_act", *train_scope = "heads_train";
+  static constexpr const char *act_kernel = "heads_act_kernel", *train_kernel = "heads_train_kernel",
+                              *train_lds_kernel = "heads_train_lds_kernel";
+  static double act_row_bytes(const Act&) { return 16.0; }
+  static double train_row_bytes(const Train& a) { return a.loss_kind == LOSS_A2C ? 20.0 : 32.0; }
+  // built once per loss kind instead of with the run-time branch (heads_common.h, LOSS_RT):
+  // 96 -> 100, 165 -> 169 and 253 -> 257 VGPRs with it
+  static constexpr bool split_loss(int HC, int AMAX, bool FAST) {
+    return AMAX == 8 && ((HC == 1 && FAST) || (HC == 4 && !FAST) || (HC == 8 && !FAST));
+  }
+  template <int HC, int AMAX, bool FAST>
+  static void launch_act(const Act& c, unsigned blocks, hipStream_t st) {
+    heads_act_kernel<HC, AMAX, FAST><<<blocks, 64 * HW, 0, st>>>(c.feat, c.feat_v, c.N, c.H, c.wc, c.bc, c.wa, c.ba, c.A,
                                                          c.noise, c.seed, c.counter, c.counter_p, c.det, c.given, c.v,
-                                                         c.act, c.lp, c.ent, rpw);
-  PPO_LAUNCH_CHECK("heads_act_kernel");
-  return 0;
-}
-
-template <int AMAX>
-int dispatch_act(int HC, const ActCall& c, hipStream_t st) {
-  switch (HC) {
-    case 1: return launch_act<1, AMAX>(c, st);
-    case 2: return launch_act<2, AMAX>(c, st);
-    case 4: return launch_act<4, AMAX>(c, st);
-    case 8: return launch_act<8, AMAX>(c, st);
+                                                         c.act, c.lp, c.ent, c.rows_per_wave);
   }
-  ppo_set_error("heads: hidden size %d not supported (<= 512)", c.H);
-  return PPO_EARG;
-}
-
-// ppo_heads_act / ppo_heads_act_dc after their argument checks
-int heads_act(const char* name, const ActCall& c, void* stream) {
-  PPO_REQUIRE(c.N >= 0 && c.A >= 1 && c.A <= 16, "%s: N=%d A=%d (1..16 actions)", name, c.N, c.A);
-  PPO_REQUIRE(c.H > 0 && c.H <= 512, "%s: hidden size %d (1..512)", name, c.H);
-  ProfScope prof("heads_act", as_stream(stream), (double)c.N * (4.0 * c.H * (c.feat_v ? 2 : 1) + 16.0));
-  if (c.N == 0) return 0;
-  if (c.A <= 8) return dispatch_act<8>(hc_of(c.H), c, as_stream(stream));
-  return dispatch_act<16>(hc_of(c.H), c, as_stream(stream));
-}
-
-// *counter += by, after the act kernel that read it (stream order): an increment inside
-// that kernel would race with the blocks that have not read the word yet
-__global__ void rng_advance_kernel(unsigned long long* counter, unsigned long long by) { *counter += by; }
-
-// the instantiations built once per loss kind instead of with the run-time branch
-// (heads_common.h, LOSS_RT): 96 -> 100, 165 -> 169 and 253 -> 257 VGPRs with it
-constexpr bool split_loss(int HC, int AMAX, bool FAST) {
-  return AMAX == 8 && ((HC == 1 && FAST) || (HC == 4 && !FAST) || (HC == 8 && !FAST));
-}
-
-template <int HC, int AMAX, bool FAST>
-void launch_train_reg(const TrainArgs& a, int blocks, hipStream_t st) {
-  if constexpr (split_loss(HC, AMAX, FAST)) {
-    if (a.loss_kind == LOSS_A2C)
-      heads_train_kernel<HC, AMAX, FAST, LOSS_A2C><<<blocks, 64 * HW, 0, st>>>(a);
-    else
-      heads_train_kernel<HC, AMAX, FAST, LOSS_PPO><<<blocks, 64 * HW, 0, st>>>(a);
-  } else {
-    heads_train_kernel<HC, AMAX, FAST, LOSS_RT><<<blocks, 64 * HW, 0, st>>>(a);
+  template <int HC, int AMAX, bool FAST, int LK>
+  static void launch_train(const Train& a, int blocks, hipStream_t st) {
+    heads_train_kernel<HC, AMAX, FAST, LK><<<blocks, 64 * HW, 0, st>>>(a);
   }
-}
-
-template <int HC, int AMAX>
-int launch_train(const TrainArgs& a, int blocks, hipStream_t st) {
-  // ppo_tune_set("heads_lds", 0): the register-weight kernel (A/B)
-  if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
-      ((uintptr_t)a.feat & 15) == 0 && ((uintptr_t)a.dfeat & 15) == 0 && ((uintptr_t)a.part_w & 15) == 0) {
+  static void launch_train_lds(const Train& a, int blocks, hipStream_t st) {
     heads_train_lds_kernel<<<blocks, 64 * HW, 0, st>>>(a);
-    PPO_LAUNCH_CHECK("heads_train_lds_kernel");
-    return 0;
   }
-  if (a.A == AMAX && a.H == 64 * HC && !a.feat_v && !a.dfeat_v)
-    launch_train_reg<HC, AMAX, true>(a, blocks, st);
-  else
-    launch_train_reg<HC, AMAX, false>(a, blocks, st);
-  PPO_LAUNCH_CHECK("heads_train_kernel");
-  return 0;
+};
+
+// ppo_heads_act (counter_p NULL) / ppo_heads_act_dc (the counter in device memory)
+int cat_act(const char* name, const float* feat, const float* feat_v, int N, int H, const float* wc, const float* bc,
+            const float* wa, const float* ba, int A, const float* noise, unsigned long long seed,
+            unsigned long long counter, const unsigned long long* counter_p, int deterministic, const int64_t* given,
+            float* value, int64_t* action, float* logp, float* entropy, void* stream) {
+  const ActCall c = {feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, counter_p, deterministic, given,
+                     value, action, logp, entropy, /*rows_per_wave*/ 0};
+  return heads_act<Cat>(name, c, stream);
 }
 
-template <int AMAX>
-int dispatch_train(int HC, const TrainArgs& a, int blocks, hipStream_t st) {
-  switch (HC) {
-    case 1: return launch_train<1, AMAX>(a, blocks, st);
-    case 2: return launch_train<2, AMAX>(a, blocks, st);
-    case 4: return launch_train<4, AMAX>(a, blocks, st);
-    case 8: return launch_train<8, AMAX>(a, blocks, st);
-  }
-  ppo_set_error("heads: hidden size %d not supported (<= 512)", a.H);
-  return PPO_EARG;
+// ppo_heads_train (LOSS_PPO) / ppo_heads_train_a2c (LOSS_A2C: old_logp, adv and vpred NULL,
+// clip and use_clipped_value_loss 0, none of them read)
+int cat_train(const char* name, int loss_kind, const float* feat, const float* feat_v, int B, int H, const float* wc,
+              const float* bc, const float* wa, const float* ba, int A, const int64_t* idx, long long row0,
+              const int64_t* actions, const float* old_logp, const float* adv, const float* vpred, const float* ret,
+              float clip, float value_coef, float entropy_coef, float inv_b, int use_clipped_value_loss, int feat_act,
+              float* dfeat, float* dfeat_v, float* part_w, float* part_b, float* part_loss, void* stream) {
+  const TrainArgs a = {feat, feat_v, B, H, A, wc, bc, wa, ba, idx, row0, actions, old_logp, adv, vpred, ret,
+                       clip, value_coef, entropy_coef, inv_b, use_clipped_value_loss, loss_kind, feat_act,
+                       dfeat, dfeat_v, part_w, part_b, part_loss, /*rows_per_wave*/ 0};
+  return heads_train<Cat>(name, a, stream);
 }
 
 }  // namespace
@@ -647,9 +557,8 @@ PPO_API int ppo_heads_act(const float* feat, const float* feat_v, int N, int H, 
                           const float* ba, int A, const float* noise, unsigned long long seed,
                           unsigned long long counter, int deterministic, const int64_t* given, float* value,
                           int64_t* action, float* logp, float* entropy, void* stream) {
-  const ActCall c = {feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, nullptr, deterministic, given,
-                     value, action, logp, entropy};
-  return heads_act("ppo_heads_act", c, stream);
+  return cat_act("ppo_heads_act", feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, counter, nullptr, deterministic,
+                 given, value, action, logp, entropy, stream);
 }
 
 // ppo_heads_act with the counter in device memory: one 8-byte word that the kernel reads
@@ -660,9 +569,8 @@ PPO_API int ppo_heads_act_dc(const float* feat, const float* feat_v, int N, int 
                              const unsigned long long* counter, int deterministic, const int64_t* given,
                              float* value, int64_t* action, float* logp, float* entropy, void* stream) {
   PPO_REQUIRE(counter != nullptr, "ppo_heads_act_dc: counter is NULL (a device pointer to one 8-byte word)");
-  const ActCall c = {feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, 0ull, counter, deterministic, given,
-                     value, action, logp, entropy};
-  return heads_act("ppo_heads_act_dc", c, stream);
+  return cat_act("ppo_heads_act_dc", feat, feat_v, N, H, wc, bc, wa, ba, A, noise, seed, 0ull, counter, deterministic,
+                 given, value, action, logp, entropy, stream);
 }
 
 // *counter += by (64-bit wrap-around) as a launch of its own on `stream`
@@ -678,25 +586,6 @@ PPO_API int ppo_heads_train_blocks(int B) {
   return (int)ceil_div(B, HW * rpw);
 }
 
-namespace {
-
-// ppo_heads_train / ppo_heads_train_a2c: one argument check, launch shape and kernel
-// selection; the entry points differ in the row loss and in the storage planes it reads
-int heads_train(const char* name, TrainArgs a, void* stream) {
-  PPO_REQUIRE(a.B > 0 && a.A >= 1 && a.A <= 16, "%s: B=%d A=%d", name, a.B, a.A);
-  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
-  ProfScope prof("heads_train", as_stream(stream),
-                 (double)a.B * (8.0 * a.H * (a.feat_v ? 2 : 1) + (a.idx ? 8.0 : 0.0) +
-                                (a.loss_kind == LOSS_A2C ? 20.0 : 32.0)));
-  a.rows_per_wave = 32;
-  const int blocks = ppo_heads_train_blocks(a.B);
-  hipStream_t st = as_stream(stream);
-  if (a.A <= 8) return dispatch_train<8>(hc_of(a.H), a, blocks, st);
-  return dispatch_train<16>(hc_of(a.H), a, blocks, st);
-}
-
-}  // namespace
-
 PPO_API int ppo_heads_train(const float* feat, const float* feat_v, int B, int H, const float* wc, const float* bc,
                             const float* wa,
                             const float* ba, int A, const int64_t* idx, long long row0, const int64_t* actions,
@@ -704,16 +593,9 @@ PPO_API int ppo_heads_train(const float* feat, const float* feat_v, int B, int H
                             float value_coef, float entropy_coef, float inv_b, int use_clipped_value_loss,
                             int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
                             float* part_loss, void* stream) {
-  TrainArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = old_logp; a.adv = adv; a.vpred = vpred; a.ret = ret;
-  a.clip = clip; a.value_coef = value_coef; a.entropy_coef = entropy_coef; a.inv_b = inv_b;
-  a.use_clipped_value_loss = use_clipped_value_loss;
-  a.loss_kind = LOSS_PPO;
-  a.feat_act = feat_act;
-  a.dfeat_v = dfeat_v;
-  a.dfeat = dfeat; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  return heads_train("ppo_heads_train", a, stream);
+  return cat_train("ppo_heads_train", LOSS_PPO, feat, feat_v, B, H, wc, bc, wa, ba, A, idx, row0, actions, old_logp,
+                   adv, vpred, ret, clip, value_coef, entropy_coef, inv_b, use_clipped_value_loss, feat_act, dfeat,
+                   dfeat_v, part_w, part_b, part_loss, stream);
 }
 
 // ppo_heads_train with A2C's row loss (algo/a2c_acktr.py:48-51, a2c_row_loss): reads only
@@ -724,38 +606,20 @@ PPO_API int ppo_heads_train_a2c(const float* feat, const float* feat_v, int B, i
                                 long long row0, const int64_t* actions, const float* ret, float value_coef,
                                 float entropy_coef, float inv_b, int feat_act, float* dfeat, float* dfeat_v,
                                 float* part_w, float* part_b, float* part_loss, void* stream) {
-  TrainArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = nullptr; a.adv = nullptr; a.vpred = nullptr;
-  a.ret = ret;
-  a.clip = 0.f; a.value_coef = value_coef; a.entropy_coef = entropy_coef; a.inv_b = inv_b;
-  a.use_clipped_value_loss = 0;
-  a.loss_kind = LOSS_A2C;
-  a.feat_act = feat_act;
-  a.dfeat_v = dfeat_v;
-  a.dfeat = dfeat; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  return heads_train("ppo_heads_train_a2c", a, stream);
+  return cat_train("ppo_heads_train_a2c", LOSS_A2C, feat, feat_v, B, H, wc, bc, wa, ba, A, idx, row0, actions, nullptr,
+                   nullptr, nullptr, ret, 0.f, value_coef, entropy_coef, inv_b, 0, feat_act, dfeat, dfeat_v, part_w,
+                   part_b, part_loss, stream);
 }
 
-// Σ over the heads_train blocks (fixed order) -> head gradients; losses -> loss_acc.
-// part_loss slot 0 is halved (0.5·Σ/B): PPO's kernels store Σ of the row's squared error
-// there, the A2C launches Σ 2 (R - v)^2, so both come out as their algorithm's value loss
+// Σ over the heads_train blocks (fixed order) -> head gradients; losses -> loss_acc
+// (heads_reduce, which also says how slot 0 comes out as either algorithm's value loss)
 PPO_API int ppo_heads_reduce(const float* part_w, const float* part_b, const float* part_loss, int nblk, int H, int A,
                              float* g_wc, float* g_bc, float* g_wa, float* g_ba, double* loss_acc, double inv_b,
                              float scale, int use_clipped_value_loss, void* stream) {
   (void)use_clipped_value_loss;  // both value losses are 0.5·mean(·)
   ProfScope prof("heads_reduce", as_stream(stream), 4.0 * nblk * (1.0 + A) * (H + 1));
-  const long long NO = 1 + A;
-  int rc;
-  if ((rc = ppo_colsum(part_w, NO * H, nblk, H, g_wc, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_w + H, NO * H, nblk, (long long)A * H, g_wa, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_b, NO, nblk, 1, g_bc, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_b + 1, NO, nblk, A, g_ba, scale, 0, stream))) return rc;
-  if (loss_acc) {
-    loss_reduce_kernel<<<1, 256, 0, as_stream(stream)>>>(part_loss, nblk, loss_acc, inv_b);
-    PPO_LAUNCH_CHECK("loss_reduce_kernel");
-  }
-  return 0;
+  return heads_reduce(part_w, part_b, 1 + A, part_loss, nblk, H, A, g_wc, g_bc, g_wa, g_ba, loss_acc, inv_b, scale,
+                      stream);
 }
 
 PPO_API int ppo_mean_f32(const float* x, long long n, float* out, void* stream) {

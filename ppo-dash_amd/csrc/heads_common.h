@@ -1,7 +1,9 @@
-// Pieces shared by the Categorical (heads.hip) and DiagGaussian (heads_gauss.hip)
-// head kernels: the per-lane head-weight registers, the 1 + A wave-reduced dot
-// products, the sampling counter's source, the activation gradient and the
-// loss-partial reduction.
+// Device pieces shared by the Categorical (heads.hip), DiagGaussian (heads_gauss.hip)
+// and Bernoulli (heads_bern.hip) head kernels: the per-lane head-weight registers, the
+// 1 + A wave-reduced dot products, the sampling counter's source, the activation
+// gradient, the loss kinds with PPO's and A2C's row loss, the per-row storage scalars
+// of the two float-action families and the loss-partial reduction.  The host side
+// (kernel selection, reduce) is heads_dispatch.h.
 #pragma once
 #include "common.h"
 
@@ -97,6 +99,85 @@ __device__ __forceinline__ void a2c_row_loss(float v, float lp, float R, float v
   s_vl += 2.f * (adv * adv);
   s_al += adv * lp;
 }
+
+// x of lane j, in every lane (j wave-uniform)
+__device__ __forceinline__ float bcast(float x, int j) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
+}
+
+// bcast(x, j) that is done where the value is converted to float, not where it is written
+struct LaneOf {
+  float x;
+  int j;
+  __device__ __forceinline__ operator float() const { return bcast(x, j); }
+};
+
+// PPO's row loss (algo/ppo.py:61-77) from the row's value v, log-prob lp and its stored
+// advantage, old log-prob, value prediction vo and return R: clipped surrogate and the
+// clipped or plain value loss, with autograd's tie conventions (0.5 each way) in g_logp, g_v.
+// Args: a *TrainArgs.  F: float, or LaneOf in the Categorical kernels, which keep their
+// three readlanes at the places of use below (hoisted to the call, the compiler schedules
+// every one of their train kernels that has this branch differently).
+template <class Args, class F>
+__device__ __forceinline__ void ppo_row_loss(const Args& a, float v, float lp, F adv_of, F olp_of, F vo_of,
+                                             float R, float& g_logp, float& g_v, float& s_vl, float& s_al) {
+  const float clip = a.clip;
+  // action loss (ppo.py:61-66)
+  const float adv = adv_of;
+  const float ratio = expf(lp - (float)olp_of);
+  const float surr1 = ratio * adv;
+  const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
+  const float surr2 = rc * adv;
+  const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
+  const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
+  g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+  // value loss (ppo.py:68-77)
+  const float vo = vo_of;
+  float vl_row;
+  if (a.use_clipped_value_loss) {
+    const float dv = v - vo;
+    const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
+    const float l1 = (v - R) * (v - R);
+    const float l2 = (vpc - R) * (vpc - R);
+    vl_row = fmaxf(l1, l2);
+    const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
+    const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
+    g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (v - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
+  } else {
+    vl_row = (R - v) * (R - v);
+    g_v = a.value_coef * a.inv_b * (v - R);
+  }
+  s_vl += vl_row;
+  s_al += fminf(surr1, surr2);
+}
+
+// Per-row storage scalars of the DiagGaussian and Bernoulli train kernels (Args: their
+// *TrainArgs): the minibatch gather idx -> advantage, old log-prob, value, return of all
+// of the wave's rows are fetched up front, lane j holding row r0 + j (rows_per_wave <= 64),
+// and broadcast per row, so no row waits on two dependent loads.
+struct RowScalars {
+  float adv = 0.f, olp = 0.f, vo = 0.f, ret = 0.f;
+  int sr_lo = 0, sr_hi = 0;   // storage row (the action plane is read per row, one row ahead)
+  template <class Args>
+  __device__ __forceinline__ void load(const Args& a, int loss_kind, long long r0, int lane) {
+    if (lane < a.rows_per_wave && r0 + lane < a.B) {
+      const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
+      sr_lo = (int)(sr & 0xffffffffll);
+      sr_hi = (int)(sr >> 32);
+      if (loss_kind != LOSS_A2C) {   // A2C: the three pointers may be NULL
+        adv = a.adv[sr];
+        olp = a.old_logp[sr];
+        vo = a.vpred[sr];
+      }
+      ret = a.ret[sr];
+    }
+  }
+  __device__ __forceinline__ long long storage_row(int j) const {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane(sr_lo, j);
+    const long long hi = __builtin_amdgcn_readlane(sr_hi, j);
+    return (hi << 32) | (long long)lo;
+  }
+};
 
 // loss partials -> acc[0..3] += {0.5·Σvl/B, -Σal/B, Σent/B, # bad actions} (double, fixed order)
 // (slot 0 of a LOSS_A2C launch holds Σ 2 (R - v)^2, so 0.5·Σ/B is mean((R - v)^2) there)

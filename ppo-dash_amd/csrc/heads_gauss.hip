@@ -19,8 +19,7 @@
 //   dL/ds_o  = Σ_rows g_logp ((a_o - mu_o)^2 / sigma_o^2 - 1) - entropy_coef
 // The entropy does not depend on the row (d mean(entropy)/d s_o = 1), so its
 // term is added once per launch, by block 0.
-#include "heads_common.h"
-#include "tune.h"
+#include "heads_dispatch.h"
 
 namespace {
 
@@ -174,43 +173,14 @@ struct GaussTrainArgs {
   int rows_per_wave;
 };
 
-// per-row storage scalars, lane j holding row r0 + j of the wave (see heads.hip)
-struct RowScalars {
-  float adv = 0.f, olp = 0.f, vo = 0.f, ret = 0.f;
-  int sr_lo = 0, sr_hi = 0;   // storage row (the action plane is read per row, one row ahead)
-  __device__ __forceinline__ void load(const GaussTrainArgs& a, int loss_kind, long long r0, int lane) {
-    if (lane < a.rows_per_wave && r0 + lane < a.B) {
-      const long long sr = a.idx ? (long long)a.idx[r0 + lane] : a.row0 + r0 + lane;
-      sr_lo = (int)(sr & 0xffffffffll);
-      sr_hi = (int)(sr >> 32);
-      if (loss_kind != LOSS_A2C) {   // A2C: the three pointers may be NULL
-        adv = a.adv[sr];
-        olp = a.old_logp[sr];
-        vo = a.vpred[sr];
-      }
-      ret = a.ret[sr];
-    }
-  }
-  __device__ __forceinline__ long long storage_row(int j) const {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane(sr_lo, j);
-    const long long hi = __builtin_amdgcn_readlane(sr_hi, j);
-    return (hi << 32) | (long long)lo;
-  }
-};
-
-__device__ __forceinline__ float bcast(float x, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
-}
-
 // Loss terms and head gradients of one row (every lane computes the same values):
-// ratio / clip / surrogate and the value loss exactly as heads_train_kernel, then
-// dL/dmu and the row's dL/dlogstd term added to gs.
+// the row loss of the launch's kind (heads_common.h), then dL/dmu and the row's
+// dL/dlogstd term added to gs.
 template <int AMAX>
 __device__ __forceinline__ void gauss_row(const GaussTrainArgs& a, int loss_kind, int A, const GaussC<AMAX>& gc, float value,
                                           const float (&mu)[AMAX], const float (&act)[AMAX], float adv, float olp,
                                           float vo, float R, float& g_v, float (&gmu)[AMAX], float (&gs)[AMAX],
                                           float& s_vl, float& s_al, float& s_bad) {
-  const float clip = a.clip;
   bool bad = false;
 #pragma unroll
   for (int o = 0; o < AMAX; ++o)
@@ -221,31 +191,7 @@ __device__ __forceinline__ void gauss_row(const GaussTrainArgs& a, int loss_kind
   if (loss_kind == LOSS_A2C) {
     a2c_row_loss(value, lp, R, a.value_coef, a.inv_b, g_logp, g_v, s_vl, s_al);   // a2c_acktr.py:48-51
   } else {
-    // action loss (ppo.py:61-66)
-    const float ratio = expf(lp - olp);
-    const float surr1 = ratio * adv;
-    const float rc = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
-    const float surr2 = rc * adv;
-    const float w1 = surr1 < surr2 ? 1.f : (surr1 == surr2 ? 0.5f : 0.f);
-    const float inr = (ratio >= 1.0f - clip && ratio <= 1.0f + clip) ? 1.f : 0.f;
-    g_logp = -a.inv_b * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
-    // value loss (ppo.py:68-77)
-    float vl_row;
-    if (a.use_clipped_value_loss) {
-      const float dv = value - vo;
-      const float vpc = vo + fminf(fmaxf(dv, -clip), clip);
-      const float l1 = (value - R) * (value - R);
-      const float l2 = (vpc - R) * (vpc - R);
-      vl_row = fmaxf(l1, l2);
-      const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-      const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-      g_v = a.value_coef * 0.5f * a.inv_b * (u1 * 2.f * (value - R) + (1.f - u1) * 2.f * (vpc - R) * vin);
-    } else {
-      vl_row = (R - value) * (R - value);
-      g_v = a.value_coef * a.inv_b * (value - R);
-    }
-    s_vl += vl_row;
-    s_al += fminf(surr1, surr2);
+    ppo_row_loss(a, value, lp, adv, olp, vo, R, g_logp, g_v, s_vl, s_al);   // ppo.py:61-77
   }
 #pragma unroll
   for (int o = 0; o < AMAX; ++o) {
@@ -522,98 +468,53 @@ __global__ __launch_bounds__(64 * HW) void gauss_train_lds_kernel(const GaussTra
   gauss_store_scalars<A>(a, A, redb, lane, wave, gbc, gba, gs, s_vl, s_al, s_ent, s_bad);
 }
 
-template <int HC, int AMAX>
-int launch_act(const ActArgs& a, hipStream_t st) {
-  const unsigned blocks = ceil_div(a.N, HW * a.rows_per_wave);
-  if (a.A == AMAX && a.H == 64 * HC && !a.feat_v)
-    gauss_act_kernel<HC, AMAX, true><<<blocks, 64 * HW, 0, st>>>(a);
-  else
-    gauss_act_kernel<HC, AMAX, false><<<blocks, 64 * HW, 0, st>>>(a);
-  PPO_LAUNCH_CHECK("gauss_act_kernel");
-  return 0;
-}
-
-template <int AMAX>
-int dispatch_act(int HC, const ActArgs& a, hipStream_t st) {
-  switch (HC) {
-    case 1: return launch_act<1, AMAX>(a, st);
-    case 2: return launch_act<2, AMAX>(a, st);
-    case 4: return launch_act<4, AMAX>(a, st);
-    case 8: return launch_act<8, AMAX>(a, st);
+// what heads_dispatch.h needs to know of this family
+struct Gauss {
+  using Act = ActArgs;
+  using Train = GaussTrainArgs;
+  static constexpr const char* noun = "action dimensions";
+  static constexpr const char *act_scope = "heads_gauss_act", *train_scope = "heads_gauss_train";
+  static constexpr const char *act_kernel = "gauss_act_kernel", *train_kernel = "gauss_train_kernel",
+                              *train_lds_kernel = "gauss_train_lds_kernel";
+  static double act_row_bytes(const Act& a) { return 12.0 + 4.0 * a.A; }
+  static double train_row_bytes(const Train& a) { return (a.loss_kind == LOSS_A2C ? 12.0 : 24.0) + 4.0 * a.A; }
+  static constexpr bool split_loss(int HC, int AMAX, bool FAST) { return AMAX == 8 && HC == 1 && !FAST; }
+  template <int HC, int AMAX, bool FAST>
+  static void launch_act(const Act& a, unsigned blocks, hipStream_t st) {
+    gauss_act_kernel<HC, AMAX, FAST><<<blocks, 64 * HW, 0, st>>>(a);
   }
-  ppo_set_error("heads: hidden size %d not supported (<= 512)", a.H);
-  return PPO_EARG;
-}
-
-// the instantiation built once per loss kind instead of with the run-time branch
-// (heads_common.h, LOSS_RT)
-constexpr bool split_loss(int HC, int AMAX, bool FAST) { return AMAX == 8 && HC == 1 && !FAST; }
-
-template <int HC, int AMAX, bool FAST>
-void launch_train_reg(const GaussTrainArgs& a, int blocks, hipStream_t st) {
-  if constexpr (split_loss(HC, AMAX, FAST)) {
-    if (a.loss_kind == LOSS_A2C)
-      gauss_train_kernel<HC, AMAX, FAST, LOSS_A2C><<<blocks, 64 * HW, 0, st>>>(a);
-    else
-      gauss_train_kernel<HC, AMAX, FAST, LOSS_PPO><<<blocks, 64 * HW, 0, st>>>(a);
-  } else {
-    gauss_train_kernel<HC, AMAX, FAST, LOSS_RT><<<blocks, 64 * HW, 0, st>>>(a);
+  template <int HC, int AMAX, bool FAST, int LK>
+  static void launch_train(const Train& a, int blocks, hipStream_t st) {
+    gauss_train_kernel<HC, AMAX, FAST, LK><<<blocks, 64 * HW, 0, st>>>(a);
   }
-}
-
-template <int HC, int AMAX>
-int launch_train(const GaussTrainArgs& a, int blocks, hipStream_t st) {
-  if (tune_heads_lds() && HC == 8 && AMAX == 8 && a.A == 8 && a.H == 512 && !a.feat_v && !a.dfeat_v &&
-      ((uintptr_t)a.feat & 15) == 0 && ((uintptr_t)a.dfeat & 15) == 0 && ((uintptr_t)a.part_w & 15) == 0) {
+  static void launch_train_lds(const Train& a, int blocks, hipStream_t st) {
     gauss_train_lds_kernel<<<blocks, 64 * HW, 0, st>>>(a);
-    PPO_LAUNCH_CHECK("gauss_train_lds_kernel");
-    return 0;
   }
-  if (a.A == AMAX && a.H == 64 * HC && !a.feat_v && !a.dfeat_v)
-    launch_train_reg<HC, AMAX, true>(a, blocks, st);
-  else
-    launch_train_reg<HC, AMAX, false>(a, blocks, st);
-  PPO_LAUNCH_CHECK("gauss_train_kernel");
-  return 0;
+};
+
+// ppo_heads_gauss_act (counter_p NULL) / ppo_heads_gauss_act_dc (the counter in device memory)
+int gauss_act(const char* name, const float* feat, const float* feat_v, int N, int H, const float* wc,
+              const float* bc, const float* wa, const float* ba, const float* logstd, int A, const float* noise,
+              unsigned long long seed, unsigned long long counter, const unsigned long long* counter_p,
+              int deterministic, const float* given, float* value, float* action, float* logp, float* entropy,
+              void* stream) {
+  const ActArgs a = {feat, feat_v, N, H, A, wc, bc, wa, ba, logstd, noise, seed, counter, counter_p,
+                     deterministic, given, value, action, logp, entropy, /*rows_per_wave*/ 0};
+  return heads_act<Gauss>(name, a, stream);
 }
 
-template <int AMAX>
-int dispatch_train(int HC, const GaussTrainArgs& a, int blocks, hipStream_t st) {
-  switch (HC) {
-    case 1: return launch_train<1, AMAX>(a, blocks, st);
-    case 2: return launch_train<2, AMAX>(a, blocks, st);
-    case 4: return launch_train<4, AMAX>(a, blocks, st);
-    case 8: return launch_train<8, AMAX>(a, blocks, st);
-  }
-  ppo_set_error("heads: hidden size %d not supported (<= 512)", a.H);
-  return PPO_EARG;
-}
-
-// ppo_heads_gauss_act / ppo_heads_gauss_act_dc after the latter's counter check
-int gauss_act(const char* name, ActArgs a, void* stream) {
-  PPO_REQUIRE(a.N >= 0 && a.A >= 1 && a.A <= 16, "%s: N=%d A=%d (1..16 action dimensions)", name, a.N, a.A);
-  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
-  ProfScope prof("heads_gauss_act", as_stream(stream),
-                 (double)a.N * (4.0 * a.H * (a.feat_v ? 2 : 1) + 12.0 + 4.0 * a.A));
-  if (a.N == 0) return 0;
-  // as ppo_heads_act: ~4096 waves in flight, one row per wave at a rollout batch of 4,096
-  a.rows_per_wave = (int)std::min<long long>(8, std::max<long long>(1, ceil_div(a.N, 4096)));
-  if (a.A <= 8) return dispatch_act<8>(hc_of(a.H), a, as_stream(stream));
-  return dispatch_act<16>(hc_of(a.H), a, as_stream(stream));
-}
-
-// ppo_heads_gauss_train / ppo_heads_gauss_train_a2c: one argument check, launch shape and
-// kernel selection
-int gauss_train(const char* name, GaussTrainArgs a, void* stream) {
-  PPO_REQUIRE(a.B > 0 && a.A >= 1 && a.A <= 16, "%s: B=%d A=%d", name, a.B, a.A);
-  PPO_REQUIRE(a.H > 0 && a.H <= 512, "%s: hidden size %d (1..512)", name, a.H);
-  ProfScope prof("heads_gauss_train", as_stream(stream),
-                 (double)a.B * (8.0 * a.H * (a.feat_v ? 2 : 1) + (a.idx ? 8.0 : 0.0) +
-                                (a.loss_kind == LOSS_A2C ? 12.0 : 24.0) + 4.0 * a.A));
-  a.rows_per_wave = 32;
-  const int blocks = ppo_heads_train_blocks(a.B);
-  if (a.A <= 8) return dispatch_train<8>(hc_of(a.H), a, blocks, as_stream(stream));
-  return dispatch_train<16>(hc_of(a.H), a, blocks, as_stream(stream));
+// ppo_heads_gauss_train (LOSS_PPO) / ppo_heads_gauss_train_a2c (LOSS_A2C: old_logp, adv and vpred
+// NULL, clip and use_clipped_value_loss 0, none of them read)
+int gauss_train(const char* name, int loss_kind, const float* feat, const float* feat_v, int B, int H,
+                const float* wc, const float* bc, const float* wa, const float* ba, const float* logstd, int A,
+                const int64_t* idx, long long row0, const float* actions, const float* old_logp, const float* adv,
+                const float* vpred, const float* ret, float clip, float value_coef, float entropy_coef, float inv_b,
+                int use_clipped_value_loss, int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
+                float* part_loss, void* stream) {
+  const GaussTrainArgs a = {feat, feat_v, B, H, A, wc, bc, wa, ba, logstd, idx, row0, actions, old_logp, adv, vpred,
+                            ret, clip, value_coef, entropy_coef, inv_b, use_clipped_value_loss, loss_kind, feat_act,
+                            dfeat, dfeat_v, part_w, part_b, part_loss, /*rows_per_wave*/ 0};
+  return heads_train<Gauss>(name, a, stream);
 }
 
 }  // namespace
@@ -628,12 +529,8 @@ PPO_API int ppo_heads_gauss_act(const float* feat, const float* feat_v, int N, i
                                 const float* noise, unsigned long long seed, unsigned long long counter,
                                 int deterministic, const float* given, float* value, float* action, float* logp,
                                 float* entropy, void* stream) {
-  ActArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.N = N; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.logstd = logstd; a.noise = noise; a.seed = seed; a.counter = counter; a.counter_p = nullptr;
-  a.deterministic = deterministic;
-  a.given = given; a.value = value; a.action = action; a.logp = logp; a.entropy = entropy;
-  return gauss_act("ppo_heads_gauss_act", a, stream);
+  return gauss_act("ppo_heads_gauss_act", feat, feat_v, N, H, wc, bc, wa, ba, logstd, A, noise, seed, counter, nullptr,
+                   deterministic, given, value, action, logp, entropy, stream);
 }
 
 // ppo_heads_gauss_act with the counter in device memory (see ppo_heads_act_dc): one 8-byte
@@ -644,12 +541,8 @@ PPO_API int ppo_heads_gauss_act_dc(const float* feat, const float* feat_v, int N
                                    int deterministic, const float* given, float* value, float* action, float* logp,
                                    float* entropy, void* stream) {
   PPO_REQUIRE(counter != nullptr, "ppo_heads_gauss_act_dc: counter is NULL (a device pointer to one 8-byte word)");
-  ActArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.N = N; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.logstd = logstd; a.noise = noise; a.seed = seed; a.counter = 0; a.counter_p = counter;
-  a.deterministic = deterministic;
-  a.given = given; a.value = value; a.action = action; a.logp = logp; a.entropy = entropy;
-  return gauss_act("ppo_heads_gauss_act_dc", a, stream);
+  return gauss_act("ppo_heads_gauss_act_dc", feat, feat_v, N, H, wc, bc, wa, ba, logstd, A, noise, seed, 0ull, counter,
+                   deterministic, given, value, action, logp, entropy, stream);
 }
 
 // the Gaussian ppo_heads_train: same launch shape (ppo_heads_train_blocks), float
@@ -661,13 +554,9 @@ PPO_API int ppo_heads_gauss_train(const float* feat, const float* feat_v, int B,
                                   float value_coef, float entropy_coef, float inv_b, int use_clipped_value_loss,
                                   int feat_act, float* dfeat, float* dfeat_v, float* part_w, float* part_b,
                                   float* part_loss, void* stream) {
-  GaussTrainArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.logstd = logstd; a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = old_logp; a.adv = adv;
-  a.vpred = vpred; a.ret = ret; a.clip = clip; a.value_coef = value_coef; a.entropy_coef = entropy_coef;
-  a.inv_b = inv_b; a.use_clipped_value_loss = use_clipped_value_loss; a.loss_kind = LOSS_PPO; a.feat_act = feat_act;
-  a.dfeat = dfeat; a.dfeat_v = dfeat_v; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  return gauss_train("ppo_heads_gauss_train", a, stream);
+  return gauss_train("ppo_heads_gauss_train", LOSS_PPO, feat, feat_v, B, H, wc, bc, wa, ba, logstd, A, idx, row0,
+                     actions, old_logp, adv, vpred, ret, clip, value_coef, entropy_coef, inv_b,
+                     use_clipped_value_loss, feat_act, dfeat, dfeat_v, part_w, part_b, part_loss, stream);
 }
 
 // ppo_heads_gauss_train with A2C's row loss (algo/a2c_acktr.py:48-51, a2c_row_loss): reads
@@ -677,13 +566,9 @@ PPO_API int ppo_heads_gauss_train_a2c(const float* feat, const float* feat_v, in
                                       const int64_t* idx, long long row0, const float* actions, const float* ret,
                                       float value_coef, float entropy_coef, float inv_b, int feat_act, float* dfeat,
                                       float* dfeat_v, float* part_w, float* part_b, float* part_loss, void* stream) {
-  GaussTrainArgs a;
-  a.feat = feat; a.feat_v = feat_v; a.B = B; a.H = H; a.A = A; a.wc = wc; a.bc = bc; a.wa = wa; a.ba = ba;
-  a.logstd = logstd; a.idx = idx; a.row0 = row0; a.actions = actions; a.old_logp = nullptr; a.adv = nullptr;
-  a.vpred = nullptr; a.ret = ret; a.clip = 0.f; a.value_coef = value_coef; a.entropy_coef = entropy_coef;
-  a.inv_b = inv_b; a.use_clipped_value_loss = 0; a.loss_kind = LOSS_A2C; a.feat_act = feat_act;
-  a.dfeat = dfeat; a.dfeat_v = dfeat_v; a.part_w = part_w; a.part_b = part_b; a.part_loss = part_loss;
-  return gauss_train("ppo_heads_gauss_train_a2c", a, stream);
+  return gauss_train("ppo_heads_gauss_train_a2c", LOSS_A2C, feat, feat_v, B, H, wc, bc, wa, ba, logstd, A, idx, row0,
+                     actions, nullptr, nullptr, nullptr, ret, 0.f, value_coef, entropy_coef, inv_b, 0, feat_act,
+                     dfeat, dfeat_v, part_w, part_b, part_loss, stream);
 }
 
 // Σ over the gauss_train blocks (fixed order) -> head and logstd gradients; losses -> loss_acc
@@ -691,16 +576,9 @@ PPO_API int ppo_heads_gauss_reduce(const float* part_w, const float* part_b, con
                                    int A, float* g_wc, float* g_bc, float* g_wa, float* g_ba, float* g_logstd,
                                    double* loss_acc, double inv_b, float scale, void* stream) {
   ProfScope prof("heads_gauss_reduce", as_stream(stream), 4.0 * nblk * ((1.0 + A) * H + 1.0 + 2.0 * A));
-  const long long NO = 1 + A, NB = 1 + 2 * A;
-  int rc;
-  if ((rc = ppo_colsum(part_w, NO * H, nblk, H, g_wc, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_w + H, NO * H, nblk, (long long)A * H, g_wa, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_b, NB, nblk, 1, g_bc, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_b + 1, NB, nblk, A, g_ba, scale, 0, stream))) return rc;
-  if ((rc = ppo_colsum(part_b + 1 + A, NB, nblk, A, g_logstd, scale, 0, stream))) return rc;
-  if (loss_acc) {
-    loss_reduce_kernel<<<1, 256, 0, as_stream(stream)>>>(part_loss, nblk, loss_acc, inv_b);
-    PPO_LAUNCH_CHECK("loss_reduce_kernel");
-  }
-  return 0;
+  const long long NB = 1 + 2 * A;
+  if (int rc = heads_reduce(part_w, part_b, NB, part_loss, nblk, H, A, g_wc, g_bc, g_wa, g_ba, loss_acc, inv_b, scale,
+                            stream))
+    return rc;
+  return ppo_colsum(part_b + 1 + A, NB, nblk, A, g_logstd, scale, 0, stream);
 }
