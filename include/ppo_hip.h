@@ -260,6 +260,9 @@ int ppo_colsum(const float* src, long long ld, int rows, long long cols, float* 
  *   "conv3_dgrad_group" 1 ppo_conv3_dgrad_bits on tiles of 16 images for B >= 16 (default; only
  *                 the valid taps are issued), 0 the per-image kernel everywhere (bit-identical
  *                 results; ppo_conv3_dgrad always runs the per-image kernel)
+ *   "wgrad_pipe"  1 ppo_linear_wgrad's split-bf16 kernel (N >= 128: the fc and GRU weight
+ *                 gradients) splits and stores the next k-step inside the MFMA stream
+ *                 (default), 0 after it (bit-identical results)
  *   "stagger"     schedule bits 0..15 (default 2; every value gives the same results);
  *                 larger values are refused (they select timing-anatomy paths that give
  *                 wrong results by design, accepted only by a -DPPO_DIAG build)

@@ -467,12 +467,31 @@ struct CfgS : CfgX<BM_, BN_, WM_, WN_, AKC, BKC, BIASA, false, false, BP_> {
   static constexpr bool SPLIT_STAGE = true;
 };
 
-template <class P, int NP>
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant
+template <int... I, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(std::make_integer_sequence<int, N>{}, f);
+}
+
+// the pipelined k loop (below) needs wave-uniform staging roles: one non-KC unit per
+// thread at most, A units on whole waves, B units on whole waves behind them
+template <class P>
+constexpr bool x9s_pipe_ok() {
+  constexpr int UA = (P::BM / 4) * 4, UB = (P::BN / 4) * 4;
+  return P::SPLIT_STAGE && !P::A_KC && !P::B_KC && !P::B_PLANES && UA % 64 == 0 && UB % 64 == 0 && UA + UB <= P::NT;
+}
+
+template <class P, int NP, bool PIPE = false>
 __global__ __launch_bounds__(P::NT) void igemm_x9s_kernel(const P p) {
   constexpr int BM = P::BM, BN = P::BN, NT = P::NT, WM = P::WM, WN = P::WN, BK = 32;
   constexpr int TM = BM / (16 * WM), TN = BN / (16 * WN);
   static_assert(TM * 16 * WM == BM && TN * 16 * WN == BN && WM * WN * 64 == NT, "tile config");
   static_assert(!P::A_EXACT && !P::B_EXACT, "split staging: fp32 operands");
+  static_assert(!PIPE || x9s_pipe_ok<P>(), "pipelined k loop: wave-uniform staging roles");
   constexpr bool BPL = P::B_PLANES, AKC = P::A_KC, BKC = P::B_KC;
   constexpr int NPL = NP == 1 ? 1 : 3;                      // planes staged
   constexpr int PA = BM * BK, PB = BN * BK;                 // bf16 elements per plane
@@ -615,14 +634,8 @@ __global__ __launch_bounds__(P::NT) void igemm_x9s_kernel(const P p) {
 
   const int fr = lane & 15, fg = lane >> 4;
   const bool bias_on = P::BIAS_FROM_A && n0 == 0;
-  if (nk > 0) {
-    gload(kbeg);
-    sstore(0, bias_on);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) gload(kbeg + (kt + 1) * BK);
+  // the 16x16 tiles of one k-step from stage `buf`; AFTER(i) runs after row i's MFMAs
+  auto mfma_step = [&](int buf, auto&& after) {
     const uint16_t* As = smem + buf * STAGE;
     const uint16_t* Bs = As + NPL * PA;
     Frag3 fb[TN];
@@ -635,8 +648,8 @@ __global__ __launch_bounds__(P::NT) void igemm_x9s_kernel(const P p) {
         fb[j].l = *reinterpret_cast<const bf16x8*>(Bs + 2 * PB + o);
       }
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
+    static_for<TM>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
       const int o = pl_off((wm * TM + i) * 16 + fr, fg);
       Frag3 fa;
       fa.h = *reinterpret_cast<const bf16x8*>(As + o);
@@ -646,9 +659,95 @@ __global__ __launch_bounds__(P::NT) void igemm_x9s_kernel(const P p) {
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = mma9<false, false, NP>(fa, fb[j], acc[i][j]);
+      after(ic);
+    });
+  };
+  if constexpr (PIPE) {
+    // Pipelined k loop (knob wgrad_pipe = 1).  A wave stages A units, B units or
+    // nothing, and runs the loop written for that role, so the staging of a k-step
+    // sits in one basic block with its MFMAs, no branch around it: the four
+    // split-and-store rows of the wave's unit follow the first IP rows of MFMA tiles
+    // in source order, two behind each, and hipcc schedules their VALU in among
+    // those MFMAs.  The operand registers (a role holds only its own operand) are
+    // free after the last of them, so the loads of k-step kt + 2 are issued there, in
+    // the middle of step kt, and have the rest of it and the barrier to arrive
+    // before step kt + 1 splits them.  The last two k-steps are peeled (nothing to
+    // load, nothing to stage).  LDS contents, MFMA order and the bias sums are
+    // those of the plain loop: same bits.  At the fc shape 0.610 -> 0.531 ms; IP = 1
+    // and 3 and a fixed MFMA / VALU mix by sched_group_barrier measured 1-3 % slower
+    // than IP = 2 with hipcc's own mix (profiles/fc_wgrad_pipe_ab.log).
+    constexpr int WA = UA / 64, WB = UB / 64;
+    constexpr int IP = TM < 2 ? TM : 2;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    auto run = [&](auto role_c) {
+      constexpr int ROLE = decltype(role_c)::value;   // 0 none, 1 A unit, 2 B unit
+      f32x4 r[8];                                     // the unit's 8 k of 4 rows, one k-step ahead
+      auto gl = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (ROLE == 1) r[j] = to_f32x4(p.a_load(actx[0], k0 + ak[0] + j));
+          if constexpr (ROLE == 2) r[j] = to_f32x4(bload(0, k0 + bk[0] + j));
+        }
+      };
+      auto put = [&](int buf, int q) {   // row q of the unit's four
+        uint16_t* As = smem + buf * STAGE;
+        const f32x4 x0 = {r[0][q], r[1][q], r[2][q], r[3][q]}, x1 = {r[4][q], r[5][q], r[6][q], r[7][q]};
+        if constexpr (ROLE == 1) {
+          put8(As, PA, arow[0] + q, ak[0] >> 3, x0, x1);
+          // summed whether or not this block stores it (bias_on): no branch in the k-step
+          if constexpr (P::BIAS_FROM_A)
+            bias_acc[q] += ((x0[0] + x0[1]) + (x0[2] + x0[3])) + ((x1[0] + x1[1]) + (x1[2] + x1[3]));
+        }
+        if constexpr (ROLE == 2) put8(As + NPL * PA, PB, brow[0] + q, bk[0] >> 3, x0, x1);
+      };
+      // k-step kt: STG splits step kt + 1 into the other stage, LD then loads step kt + 2
+      auto step = [&](auto stg_c, auto ld_c, int kt) {
+        constexpr bool STG = decltype(stg_c)::value && ROLE != 0, LD = decltype(ld_c)::value && ROLE != 0;
+        const int buf = kt & 1;
+        mfma_step(buf, [&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          if constexpr (STG && i < IP) {
+            constexpr int Q0 = 4 * i / IP, Q1 = 4 * (i + 1) / IP;
+#pragma unroll
+            for (int q = Q0; q < Q1; ++q) put(buf ^ 1, q);
+          }
+          if constexpr (LD && i == IP - 1) {   // pinned: hipcc otherwise sinks the loads to the barrier
+            __builtin_amdgcn_sched_barrier(0);
+            gl(kbeg + (kt + 2) * BK);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        });
+        __syncthreads();
+      };
+      if constexpr (ROLE != 0) {
+        if (nk > 0) {
+          gl(kbeg);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) put(0, q);
+          if (nk > 1) gl(kbeg + BK);
+        }
+      }
+      __syncthreads();
+      for (int kt = 0; kt + 2 < nk; ++kt) step(std::true_type{}, std::true_type{}, kt);
+      if (nk >= 2) step(std::true_type{}, std::false_type{}, nk - 2);
+      if (nk >= 1) step(std::false_type{}, std::false_type{}, nk - 1);
+    };
+    if (wv < WA) run(std::integral_constant<int, 1>{});
+    else if (wv < WA + WB) run(std::integral_constant<int, 2>{});
+    else run(std::integral_constant<int, 0>{});
+  } else {
+    if (nk > 0) {
+      gload(kbeg);
+      sstore(0, bias_on);
     }
-    if (kt + 1 < nk) sstore(buf ^ 1, bias_on);
     __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+      const int buf = kt & 1;
+      if (kt + 1 < nk) gload(kbeg + (kt + 1) * BK);
+      mfma_step(buf, [](auto) {});
+      if (kt + 1 < nk) sstore(buf ^ 1, bias_on);
+      __syncthreads();
+    }
   }
 
   bool vec_done = false;
@@ -700,6 +799,16 @@ int launch_x9(const P& p, long long M, int N, int Z, hipStream_t st, const char*
   const bool prof = ppo_prof_begin(name, st, &slot);
   const int np = tune_products();
   if constexpr (P::SPLIT_STAGE) {
+    if constexpr (x9s_pipe_ok<P>()) {
+if (tune_wgrad_pipe()) {
+        if (np == 9) igemm_x9s_kernel<P, 9, true><<<grid, P::NT, 0, st>>>(p);
+        else if (np == 1) igemm_x9s_kernel<P, 1, true><<<grid, P::NT, 0, st>>>(p);
+        else igemm_x9s_kernel<P, 6, true><<<grid, P::NT, 0, st>>>(p);
+        if (prof) ppo_prof_end(slot, st, flops);
+        PPO_LAUNCH_CHECK(name);
+        return 0;
+      }
+    }
     if (np == 9) igemm_x9s_kernel<P, 9><<<grid, P::NT, 0, st>>>(p);
     else if (np == 1) igemm_x9s_kernel<P, 1><<<grid, P::NT, 0, st>>>(p);
     else igemm_x9s_kernel<P, 6><<<grid, P::NT, 0, st>>>(p);

@@ -17,14 +17,17 @@
 //                slab stores; 0: 128 x 64 tiles (8 waves of 16 x 64), 4-B stores
 //   conv3_dgrad_group 1: ppo_conv3_dgrad_bits on 16-image tiles for B >= 16 (conv3.hip: only
 //                valid taps are issued); 0: the per-image kernel everywhere
+//   wgrad_pipe   1: the split-at-staging weight gradients (fc, GRU: igemm_x9s_kernel) stage the
+//                next k-step inside the MFMA stream, per wave role, loads issued mid-step;
+//                0: the plain loop (MFMAs, then split and store, then the barrier); same bits
 #include "common.h"
 #include "tune.h"
 
 static const char* g_tune_names[TK_N] = {"conv1_fwd", "conv1_wgrad", "x9", "fc_splitk", "rgb_aff", "fc_splitk_tile",
-                                       "conv3_dgrad_group"};
+                                       "conv3_dgrad_group", "wgrad_pipe"};
 // fc_splitk 4 with 128 x 128 tiles: 0.050-0.052 vs 0.054-0.055 ms per 4,096-row act for 2
 // slices of 128 x 64 tiles (profiles/r06_s7_fc_splitk_sweep.log)
-static int g_tune[TK_N] = {0, 9, 1, 4, 1, 1, 1};
+static int g_tune[TK_N] = {0, 9, 1, 4, 1, 1, 1, 1};
 // stagger: the image-resident kernels with two LDS stages let waves 4-7 stage the
 // next image after their compute (conv2 / conv3 dgrad)
 static int g_stagger = 2;   // bit 1 (conv2 dgrad deferred 16-B stores): measured best
@@ -41,6 +44,7 @@ int tune_products() { return g_split_products; }
 int tune_stagger() { return g_stagger; }
 int tune_small_b() { return g_small_b; }
 bool tune_heads_lds() { return g_heads_lds != 0; }
+bool tune_wgrad_pipe() { return g_tune[TK_WGRAD_PIPE] != 0; }
 
 static bool tune_ok(int k, int v) {
   switch (k) {

@@ -142,6 +142,15 @@ def main():
         call("ppo_conv3_dgrad_bits", dz3.data_ptr(), B, pk[4], m2.data_ptr(), dz2.data_ptr(), s)
         call("ppo_tune_set", b"conv3_dgrad_group", keep)
 
+    zg = zs(B, 6 * 2)   # the GRU's dW_hh (768 x 256): 6 x 2 tiles of 128 x 128, as the engine counts them
+
+    def linear_wgrad(pipe, dy, x, N, Kw, Z):
+        """the wgrad_pipe knob position for this launch only"""
+        keep = call("ppo_tune_get", b"wgrad_pipe")
+        call("ppo_tune_set", b"wgrad_pipe", pipe)
+        call("ppo_linear_wgrad", dy.data_ptr(), x.data_ptr(), B, N, Kw, Z, slab.data_ptr(), slab_b.data_ptr(), s)
+        call("ppo_tune_set", b"wgrad_pipe", keep)
+
     K = {
         "heads_train": (heads_train, 0.0),
         "heads_gauss_train": (heads_gauss_train, 0.0),
@@ -180,6 +189,12 @@ def main():
                                          dz3.data_ptr(), s), 2.0 * B * 1568 * H),
         "fc_wgrad": (lambda: call("ppo_linear_wgrad", dh.data_ptr(), a3.data_ptr(), B, H, 1568, z4, slab.data_ptr(),
                                   slab_b.data_ptr(), s), 2.0 * B * 1568 * H),
+        # the two k loops of the split-at-staging weight gradient side by side (knob wgrad_pipe = 0 / 1), at the
+        # fc shape and at the c5 GRU's dW_hh (dy [B][768], h [B][256])
+        "fc_wgrad_p0": (lambda: linear_wgrad(0, dh, a3, H, 1568, z4), 2.0 * B * 1568 * H),
+        "fc_wgrad_p1": (lambda: linear_wgrad(1, dh, a3, H, 1568, z4), 2.0 * B * 1568 * H),
+        "gru_wgrad_p0": (lambda: linear_wgrad(0, ggi, ghp, 768, 256, zg), 2.0 * B * 768 * 256),
+        "gru_wgrad_p1": (lambda: linear_wgrad(1, ggi, ghp, 768, 256, zg), 2.0 * B * 768 * 256),
         "fc_wreduce": (lambda: call("ppo_wgrad_reduce", slab.data_ptr(), slab_b.data_ptr(), z4, H, 1568, 2, 32, 49,
                                     gw.data_ptr(), gb.data_ptr(), 1.0, 0, s), 0.0),
         "conv3_dgrad": (lambda: call("ppo_conv3_dgrad", dz3.data_ptr(), B, pk[4], a2.data_ptr(), dz2.data_ptr(), s),
