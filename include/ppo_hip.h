@@ -532,6 +532,55 @@ int ppo_clip_rmsprop_guarded(float* params, float* grads, float* square_avg, lon
                              float scale, double max_norm, double lr, double alpha, double eps, double* norm_out,
                              const int* guard_i, const double* guard_d, int* skipped, void* stream);
 
+/* ---------------- GAIL discriminator (algo/gail.py) ------------------------- */
+/* trunk = Linear(D, Hd) - Tanh - Linear(Hd, Hd) - Tanh - Linear(Hd, 1).  `params` and
+ * every gradient are flat fp32 in trunk.parameters() order: W1 [Hd][D], b1 [Hd],
+ * W2 [Hd][Hd], b2 [Hd], w3 [Hd], b3 [1]; P = Hd D + Hd^2 + 3 Hd + 1.  A row of the
+ * discriminator's input is (obs | vector_obs | action) of one row of the storage planes
+ * obs [rows][obs_dim], vector_obs [rows][V] (NULL when V == 0) and actions [rows][A], all
+ * fp32, D = obs_dim + V + A.
+ *
+ * Every function checks its arguments before any HIP call and returns PPO_EARG for:
+ * Hd not a multiple of 4 in [4, 128], D < 2, D != obs_dim + V + A, B / R / T / N < 1, a
+ * NULL pointer, or a (D, Hd) whose parameters and row tile do not fit the 160 KB of LDS:
+ * ppo_gail_lds_bytes(D, Hd) (host only; -1 for sizes outside the limits above) is the
+ * larger footprint of the train and the reward kernel, 83.6 KB at D = 23, Hd = 100; Hd = 100
+ * fits up to D = 145 (the reward kernel's 64-row tile; the train kernel up to 247).
+ *
+ * ppo_gail_train: one launch of ppo_gail_train_blocks(B) blocks for the minibatch
+ *   L = BCE(d_e, 1) + BCE(d_p, 0) + lambda mean_b (|dd/dx(x_m)|_2 - 1)^2,
+ *   x_m = alpha x_e + (1 - alpha) x_p  (gail.py:30-56, 79-88)
+ * over B row triplets: policy row b is storage row idx[b] (idx NULL: row0 + b; an index
+ * outside [0, rows) reads row 0 or rows - 1, never outside the planes), expert row b is
+ * expert [B][D], alpha [B].  Each block writes its sum of the row gradients of L to
+ * part_grad [blocks][P] and {sum softplus(-d_e), sum softplus(d_p), sum (|g| - 1)^2} to
+ * part_loss [blocks][3]; nothing else is stored.  ppo_gail_reduce: grad [P] = the sum of
+ * the partials in block order (in double; independent of its launch shape), loss_acc[0]
+ * += L and loss_acc[1..3] = the three sums of this minibatch (float64 [4] on the device). */
+int ppo_gail_train_blocks(int B);
+long long ppo_gail_lds_bytes(int D, int Hd);
+int ppo_gail_train(const float* params, int D, int Hd, int B, const float* obs, int obs_dim,
+                   const float* vector_obs, int V, const float* actions, int A, long long rows, const int64_t* idx,
+                   long long row0, const float* expert, const float* alpha, float lambda, float* part_grad,
+                   float* part_loss, void* stream);
+int ppo_gail_reduce(const float* part_grad, const float* part_loss, int nblk, int P, int B, float lambda, float* grad,
+                    double* loss_acc, void* stream);
+/* out[i] = the logit d of storage row row0 + i, i < R: the reward before scaling.  (gail.py:
+ * 101-103 computes log s - log(1 - s), s = sigmoid(d): d in exact arithmetic, 3.5e-5 off at
+ * |d| = 6 and infinite from |d| = 17 in fp32.)  One launch; nothing is stored past out[R - 1]. */
+int ppo_gail_reward(const float* params, int D, int Hd, const float* obs, int obs_dim, const float* vector_obs,
+                    int V, const float* actions, int A, long long row0, long long R, float* out, void* stream);
+/* gail.py:107-111 for t = 0 .. T - 1 over N lanes, one single-block launch.  r and masks are
+ * [T][N], ret [N], rms = {mean, var, count} float64 on the device.  With update_rms:
+ *   ret = (ret * mask_t) * gamma + r_t        (fp32, one rounding per operation, gamma as fp32)
+ *   batch mean and population variance of ret: float64 sums of the fp32 values in a fixed
+ *   order (two passes), merged into rms as baselines' RunningMeanStd does
+ * then r_t = r_t / (float)sqrt(var + 1e-8) in place.  Without it ret and rms are not written
+ * and the current var scales every step.  T calls with T = 1 equal one call with T steps,
+ * bit for bit. */
+int ppo_gail_returns(float* r, const float* masks, float* ret, double* rms, int T, int N, double gamma,
+                     int update_rms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,10 @@ def get_args(argv=None):
     p.add_argument('--entropy-coef', type=float, default=0.01)
     p.add_argument('--value-loss-coef', type=float, default=0.5)
     p.add_argument('--max-grad-norm', type=float, default=0.5)
+    p.add_argument('--gail', action='store_true', default=False, help='train against a GAIL discriminator')
+    p.add_argument('--gail-experts-dir', default='./gail_experts', help='where the expert trajectory files are')
+    p.add_argument('--gail-batch-size', type=int, default=128, help='discriminator minibatch rows')
+    p.add_argument('--gail-epoch', type=int, default=5, help='discriminator updates per iteration')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--cuda-deterministic', action='store_true', default=False)
     p.add_argument('--num-processes', type=int, default=16)

@@ -12,6 +12,9 @@ RMSprop's square_avg; step count, lr) so a resumed run continues bit-identically
 
     save_checkpoint(path, actor_critic, ob_rms, agent=agent)
     actor_critic, ob_rms = load_checkpoint(path, device, agent=agent)
+
+With --gail, pass the discriminator as discr= to both: its parameters, Adam state, running
+return moments and carried returns (algo/gail.py checkpoint_state) travel in the same file.
 """
 import os
 
@@ -73,7 +76,7 @@ def policy_config(actor_critic):
             "vector_obs_len": int(cfg["vector_obs_len"])}
 
 
-def save_checkpoint(path, actor_critic, ob_rms=None, agent=None, extra=None):
+def save_checkpoint(path, actor_critic, ob_rms=None, agent=None, extra=None, discr=None):
     """Write {policy state_dict, constructor config, ob_rms, optimizer state}.
     Every tensor is copied to the host; the file holds no pickled objects."""
     d = os.path.dirname(path)
@@ -81,7 +84,8 @@ def save_checkpoint(path, actor_critic, ob_rms=None, agent=None, extra=None):
         os.makedirs(d, exist_ok=True)
     ck = {"format": FORMAT, "config": policy_config(actor_critic),
           "policy": {k: v.detach().cpu().clone() for k, v in actor_critic.state_dict().items()},
-          "ob_rms": _ob_rms_state(ob_rms), "optimizer": None, "extra": extra}
+          "ob_rms": _ob_rms_state(ob_rms), "optimizer": None, "extra": extra,
+          "gail": None if discr is None else discr.checkpoint_state()}
     if agent is not None:
         opt = agent.optimizer
         sd = opt.state_dict()
@@ -95,12 +99,13 @@ def save_checkpoint(path, actor_critic, ob_rms=None, agent=None, extra=None):
     os.replace(tmp, path)   # a crash mid-save never leaves a truncated checkpoint behind
 
 
-def load_checkpoint(path, device=None, actor_critic=None, agent=None):
+def load_checkpoint(path, device=None, actor_critic=None, agent=None, discr=None):
     """-> (actor_critic, ob_rms), as `torch.load(...)` returns them at T/run.py:64-66.
     Loads with weights_only=True.  Rebuilds the Policy from the recorded config
     unless one is passed in, or `agent` is (then agent.actor_critic is used; its
     parameters are overwritten in place); restores the optimizer state into
-    `agent` when given."""
+    `agent` when given, and the discriminator's state into `discr` (a
+    gail.Discriminator of the recorded sizes, already on its device) when given."""
     from . import model as M
 
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -144,4 +149,8 @@ def load_checkpoint(path, device=None, actor_critic=None, agent=None):
         for k in opt.STATE:
             sd[k] = None if o[k] is None else o[k].to(dev)
         opt.load_state_dict(sd)
+    if discr is not None:
+        if ck.get("gail") is None:
+            raise KeyError("%s: holds no discriminator state (saved without discr=)" % path)
+        discr.load_checkpoint_state(ck["gail"])
     return actor_critic, ob_rms
